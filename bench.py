@@ -11,9 +11,15 @@ no WORLD_SIZE it re-executes itself under torch.distributed.run (one rank per GP
 Every GEMM of the step runs on the hand-written kernels (gemm8p_pers_kernel for the large bf16-output shapes, gemm256_kernel / gemm_bf16_kernel for the rest); hipBLASLt on the plain shapes is measured BESIDE the headline as
 `vendor_comparator` (never part of `value`).
 
-Prints ONE JSON line on rank 0 (contract in the task statement) with the extra objects
-  "roofline":     dominant kernel (the bf16 MFMA GEMM): algorithmic FLOPs of all its launches / their HIP-event time
-  "cpu_baseline": the fp32 CPU oracle (oracle/, a port of the reference's CPU path) timed on a bounded sample.
+Prints ONE JSON line on rank 0 (contract in the task statement).  A plain run sets up, warms up, times --steps steps and prints the
+headline fields (metric, value, unit, higher_is_better, dtype, ms_per_step, ...); everything measured beside the headline is filled in
+only with --full (null otherwise):
+  "roofline":     dominant kernel (the bf16 MFMA GEMM): algorithmic FLOPs of all its launches / their HIP-event time (events on every
+                  third timed step), with "hbm_segments" from the same events
+  "cpu_baseline": the fp32 CPU oracle (oracle/, a port of the reference's CPU path) timed on a bounded sample, and "parity_check" against it
+  "vendor_comparator", "varlen_padded_comparator", "measured_ceiling_8k_cubed", "clock", "other_configs", "exchange_ms_per_step".
+--dump-outputs DIR writes what the last timed step computed (the loss and the floating-point loss features the caller receives) as
+DIR/<name>.npy; inputs and weights are seeded, so two builds run with the same arguments can be compared output for output.
 """
 import argparse
 import json
@@ -320,6 +326,32 @@ def other_config(kind, dev, batch=None, steps=5, warmup=2):
     return out
 
 
+DUMP_MAX_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir, loss, feats):
+    """--dump-outputs: the loss and every floating-point tensor of the loss features of the last timed step as <out_dir>/<name>.npy (float32; the
+    loss float64).  Rows beyond the 64 MB budget are replaced by a fixed, seeded sample of rows (its row indices are written beside it)."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    arrays = {"loss": np.asarray([float(loss)], dtype=np.float64)}
+    for k in sorted(feats):
+        v = feats[k]
+        if torch.is_tensor(v) and v.is_floating_point():
+            arrays[k] = v.detach().float().cpu().numpy()
+    total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_MAX_BYTES:
+        for k in [k for k in arrays if k != "loss"]:
+            a = arrays[k]
+            keep = max(1, int(a.shape[0] * DUMP_MAX_BYTES / total / 2))
+            if keep < a.shape[0]:
+                rows = np.sort(np.random.default_rng(7122).choice(a.shape[0], keep, replace=False))
+                arrays[k] = a[rows]
+                arrays[k + "_rows"] = rows.astype(np.float64)
+    for k, a in arrays.items():
+        np.save(os.path.join(out_dir, k + ".npy"), a)
+
+
 def _free_port():
     import socket
     s = socket.socket()
@@ -360,17 +392,19 @@ def dry_run(args, world, rank):
         i = torch.nn.functional.normalize(torch.randn(B, E, generator=g), dim=-1)
         f = parallel.gather_loss_feats({"id": torch.arange(B) + rank * B, "image_feat": i, "parallel_audio_feat": a})
         lg = f["parallel_audio_feat"] @ f["image_feat"].t() / 0.07
-        return 0.5 * ((torch.logsumexp(lg, 1) - lg.diagonal()).mean() + (torch.logsumexp(lg, 0) - lg.diagonal()).mean()), f["id"].shape[0]
+        return 0.5 * ((torch.logsumexp(lg, 1) - lg.diagonal()).mean() + (torch.logsumexp(lg, 0) - lg.diagonal()).mean()), f["id"].shape[0], f
     for _ in range(args.warmup):
         step()
     if world > 1:
         dist.barrier()
     t0 = time.perf_counter()
     for _ in range(args.steps):
-        loss, bg = step()
+        loss, bg, feats = step()
     if world > 1:
         dist.barrier()
     dt = time.perf_counter() - t0
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, loss, feats)
     seen = torch.ones(1)
     if world > 1:
         t = torch.tensor([dt], dtype=torch.float64)
@@ -446,12 +480,12 @@ def main():
                     "HuBERT-large + ViT-L/14 (configs[4]), informational")
     ap.add_argument("--audio-len", type=int, default=160000)
     ap.add_argument("--varlen", action="store_true", help="SURVEY.md section 8(d) C2 varlen variant: L_i ~ U{32000..160000} (seed 7122) instead of every wave at "
-                    "--audio-len; the step runs on the padding-free engine and the flop model uses each utterance's own frame count.  The same batch on the "
+                    "--audio-len; the step runs on the padding-free engine and the flop model uses each utterance's own frame count.  With --full the same batch on the "
                     "padded engine (SC_VARLEN_PACK=0) is timed beside it as `varlen_padded_comparator`")
     ap.add_argument("--global-batch", type=int, default=None, help="STRONG scaling: the global batch is fixed (e.g. 2048 = spchclp_p.yaml:10 x 8 GPUs) and split "
                     "over the ranks (pairs per GPU = global / N); the line says \"scaling\": \"strong\"")
-    ap.add_argument("--cpu-pairs", type=int, default=32, help="pairs for the CPU baseline sample (0 = skip)")
-    ap.add_argument("--no-roofline-events", action="store_true")
+    ap.add_argument("--cpu-pairs", type=int, default=32, help="--full: pairs for the CPU baseline sample (0 = skip)")
+    ap.add_argument("--no-roofline-events", action="store_true", help="--full without the roofline / HBM events")
     ap.add_argument("--train", action="store_true", help="time the TRAINING step of the trainable tail instead (forward in train mode + loss.backward() "
                     "+ grad all-reduce + clip + Adam + LR schedule); not the headline metric, reported with config.mode = 'train'")
     ap.add_argument("--finetune-layers", type=int, nargs="*", default=[], help="with --train: also fine-tune these HuBERT transformer layers "
@@ -460,11 +494,11 @@ def main():
                     "transformer layers train too; informational")
     ap.add_argument("--vocab", type=int, default=8112, help="--model cascaded: sub-word table size (8112 = the shipped reduced vocabulary, "
                     "spchclp_c.yaml:94; 49408 = the full table)")
-    ap.add_argument("--no-vendor-comparator", action="store_true", help="skip the hipBLASLt comparator run beside the headline")
-    ap.add_argument("--no-clock-probe", action="store_true", help="skip the rocm-smi clock / power reading taken beside the timed region")
+    ap.add_argument("--no-vendor-comparator", action="store_true", help="--full: skip the hipBLASLt comparator run beside the headline")
+    ap.add_argument("--no-clock-probe", action="store_true", help="--full: skip the rocm-smi clock / power reading taken beside the timed region")
     ap.add_argument("--no-other-configs", action="store_true", help="skip the short runs of the non-headline configurations (cascaded, large, varlen packed / "
-                    "padded, train) that the default N = 1 headline run reports beside `value` as `other_configs`")
-    ap.add_argument("--dump-gemm-launches", default=None, help="write the per-step list of GEMM launches (shape, epilogue, tower) as JSON: "
+                    "padded, train) that an N = 1 --full run reports beside `value` as `other_configs`")
+    ap.add_argument("--dump-gemm-launches", default=None, help="--full: write the per-step list of GEMM launches (shape, epilogue, tower) as JSON: "
                     "tools/make_traffic_json.py aligns the PMC rows of the same command with it, so `roofline.traffic` covers exactly the launches "
                     "`roofline.launches_per_step` counts")
     ap.add_argument("--graph", choices=["auto", "on", "off"], default="auto", help="replay the local part of the step (both towers + head: everything before "
@@ -473,7 +507,14 @@ def main():
     ap.add_argument("--dry-run", action="store_true", help="CPU/gloo check of the launcher + exchange protocol (no GPU, no kernels)")
     ap.add_argument("--share-gpu", action="store_true", help="TEST HOOK for 1-GPU boxes: all N ranks run on cuda:0 and exchange over gloo, so the N > 1 code "
                     "path (packed gather, global-batch loss, max-over-ranks timing) executes with the real kernels; the line says so in `data`")
+    ap.add_argument("--full", action="store_true", help="also measure everything beside the headline: roofline / HBM events on every third timed step, "
+                    "CPU baseline + parity check, hipBLASLt comparator, 8192^3 ceiling, clock / power probe, padded-engine comparator (--varlen), "
+                    "exchange timing (N > 1) and the other BASELINE.json configurations.  Off: the run does only what `value` needs")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR", help="after the timed steps, write what the last timed step computed (loss and "
+                    "the floating-point loss features) as DIR/<name>.npy (rank 0)")
     args = ap.parse_args()
+    if args.dump_gemm_launches and not args.full:
+        sys.exit("bench.py: --dump-gemm-launches needs --full (the launch list comes from the roofline events)")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:       # no launcher around us: become one
         sys.exit(self_launch(args.gpus, sys.argv[1:]))
@@ -524,10 +565,11 @@ def main():
         args.batch = 64 if large else 256
     casc = args.model == "cascaded"
     model = build_model(large=large, cascaded=casc, vocab=args.vocab, finetune_layers=args.finetune_layers if args.train else [], finetune_all=args.finetune_all and args.train)
-    sd_cpu = {k: v.clone() for k, v in model.state_dict().items()} if (rank == 0 and args.cpu_pairs > 0 and world == 1 and not args.train and not large and not casc) else None
+    sd_cpu = {k: v.clone() for k, v in model.state_dict().items()} if (args.full and rank == 0 and args.cpu_pairs > 0 and world == 1 and not args.train and not large and not casc) else None
     model = model.to(dev)
     B, L = args.batch, args.audio_len
     batch, lens = make_batch(B, L, rank, dev, args.varlen)
+    last = {}                       # the loss features of the most recent step (--dump-outputs)
 
     if args.train:
         model.train()
@@ -535,16 +577,20 @@ def main():
 
         def step():
             opt.zero_grad()
-            loss = model.training_step_end(model.training_step(batch, 0))["loss"]
+            o = model.training_step(batch, 0)
+            loss = model.training_step_end(o)["loss"]
             loss.backward()
             opt.step()
             sch["scheduler"].step()
+            last["feats"] = o["loss_feats"]
             return loss.detach()
     else:
         def step():
             with torch.no_grad():
                 lf, _, _ = model(batch)
-                return model.compute_loss(parallel.gather_loss_feats(lf))["loss"]
+                f = parallel.gather_loss_feats(lf)
+                last["feats"] = f
+                return model.compute_loss(f)["loss"]
 
     def fence():
         if world > 1:
@@ -592,7 +638,9 @@ def main():
             def replay_step():
                 graph.replay()
                 with torch.no_grad():
-                    return model.compute_loss(parallel.gather_loss_feats(g_lf))["loss"]
+                    f = parallel.gather_loss_feats(g_lf)
+                    last["feats"] = f
+                    return model.compute_loss(f)["loss"]
             l_g = float(replay_step())                             # every rank runs both forms once (the same collectives everywhere) ...
             g_copy = {k: v.detach().clone() for k, v in g_lf.items() if torch.is_tensor(v)}
             with torch.no_grad():
@@ -605,9 +653,9 @@ def main():
             else:
                 replay_step, graph_note = None, "eager (replayed step loss %.6f != eager %.6f on some rank)" % (l_g, l_e)
     fence()
-    # roofline instrumentation: HIP events around every GEMM launch of every THIRD timed step (two events per launch, ~220 launches per
+    # roofline instrumentation (--full): HIP events around every GEMM launch of every THIRD timed step (two events per launch, ~220 launches per
     # step: on every step they cost ~1 % of the step time they are meant to explain)
-    prof = None if args.no_roofline_events else []
+    prof = [] if (args.full and not args.no_roofline_events) else None
     hbm_prof, xchg_prof = [], []
     ops.PROFILE_SIDE = []
     ev_steps = 0
@@ -636,11 +684,14 @@ def main():
         torch.distributed.all_reduce(t, op=torch.distributed.ReduceOp.MAX)
         dt = t.item()
     pairs_per_s = world * B * args.steps / dt
-    # ---- beside the timed region (all ranks take part; none of it enters `value`)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, loss, last["feats"])
+    # ---- beside the timed region (all ranks take part; none of it enters `value`; --full only)
     seen = torch.ones(1, device=dev)
     exchange_ms = None
     if world > 1:
         torch.distributed.all_reduce(seen)                    # every rank of the job answered over RCCL
+    if world > 1 and args.full:
         with torch.no_grad():
             E = 768 if large else 512                          # the step's payload: ids + image + audio embeddings of this rank's pairs
             lf_x = {"id": batch["id"], "image_feat": torch.randn(B, E, device=dev), ("cascaded_audio_feat" if casc else "parallel_audio_feat"): torch.randn(B, E, device=dev)}
@@ -663,7 +714,7 @@ def main():
         exchange_in_step_ms = round(t.item(), 4)
     # the same batch on the PADDED engine (what every round before the packed engine measured): comparator, never part of `value`
     varlen_cmp = None
-    if args.varlen and not args.train:
+    if args.full and args.varlen and not args.train:
         os.environ["SC_VARLEN_PACK"] = "0"
         for _ in range(2):
             step()
@@ -683,7 +734,7 @@ def main():
                       "ms_per_step": round(vdt / nv * 1e3, 3), "value": round(world * B * nv / vdt, 2), "unit": "pairs/s"}
     # measured ceiling of the vendor library on this box, beside the 2.5 PF/s datasheet peak: hipBLASLt and the hand-written kernel on 8192^3 bf16
     ceiling = None
-    if world == 1 and not args.no_vendor_comparator and not args.train:
+    if args.full and world == 1 and not args.no_vendor_comparator and not args.train:
         n8 = 8192
         a8 = torch.randn(n8, n8, device=dev, dtype=torch.bfloat16)
         w8 = torch.randn(n8, n8, device=dev, dtype=torch.bfloat16)
@@ -703,10 +754,10 @@ def main():
         ops.set_vendor_gemm(False)
         del a8, w8, c8
     clock = None
-    if world == 1 and not args.no_clock_probe:
+    if args.full and world == 1 and not args.no_clock_probe:
         clock = clock_under_load(step, fence)
     vendor = None
-    if not args.no_vendor_comparator and not args.train:
+    if args.full and not args.no_vendor_comparator and not args.train:
         # the same step with hipBLASLt taking the plain GEMMs (QKV / out-proj / fc2 / ViT projections): a COMPARATOR for the hand-written
         # kernel on those shapes, measured with the same fences, reported beside the headline and never part of it
         ops.set_vendor_gemm(True)
@@ -873,7 +924,7 @@ def main():
             out["cpu_baseline"] = cpu_baseline(sd_cpu, args.cpu_pairs, L, keep=keep)
             if keep:
                 out["parity_check"] = parity_check(model, keep, dev)
-        if world == 1 and not args.no_other_configs and not args.train and not large and not casc and not args.varlen:
+        if args.full and world == 1 and not args.no_other_configs and not args.train and not large and not casc and not args.varlen:
             del model
             torch.cuda.empty_cache()
             oc = {}

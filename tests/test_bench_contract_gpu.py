@@ -1,18 +1,22 @@
 """bench.py prints ONE JSON line with the contract's fields (task statement: metric/value/unit/n_gpus/steps/warmup/ms_per_step/
-higher_is_better/scaling/vs_baseline/dtype/data/config + roofline + cpu_baseline).  Small batch so the check takes seconds."""
+higher_is_better/scaling/vs_baseline/dtype/data/config + roofline + cpu_baseline).  Small batch so the check takes seconds.
+The measurements beside the headline run with --full; a plain run leaves them null (test_bench_plain_run_is_lean_and_dumps_outputs)."""
 import json
 import os
+import tempfile
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
-def _run(*extra, steps=2):
-    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", str(steps), "--warmup", "1", "--batch", "8", *extra],
+def _run(*extra, steps=2, full=True):
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", str(steps), "--warmup", "1", "--batch", "8", *extra]
+                         + (["--full"] if full else []),
                          capture_output=True, text=True, timeout=900, cwd=ROOT)
     assert out.returncode == 0, out.stderr[-2000:]
     lines = [l for l in out.stdout.strip().splitlines() if l.startswith("{")]
@@ -93,3 +97,30 @@ def test_bench_eight_ranks_on_one_gpu_weak_and_strong():
     s = _run("--gpus", "8", "--share-gpu", "--cpu-pairs", "0", "--no-vendor-comparator", "--no-clock-probe", "--global-batch", "64")
     assert s["scaling"] == "strong" and s["config"]["pairs_per_gpu"] == 8 and s["config"]["global_batch"] == 64 and s["ranks_seen"] == 8
     assert s["step_launch"]["method"].startswith("eager")
+
+
+def test_bench_plain_run_is_lean_and_dumps_outputs():
+    """Without --full the line carries the headline fields and nothing measured beside them; --steps sets the timed steps, and --dump-outputs
+    writes the last timed step's loss and loss features.  The inputs are seeded: a second run with the same arguments computes the same outputs."""
+    with tempfile.TemporaryDirectory() as tmp:
+        runs = []
+        for i in range(2):
+            d = _run("--dump-outputs", os.path.join(tmp, str(i)), steps=3, full=False)
+            assert d["steps"] == 3 and d["warmup"] == 1 and d["unit"] == "pairs/s" and d["higher_is_better"] is True and d["dtype"] == "bf16"
+            assert abs(d["value"] - 8 * 1000.0 / d["ms_per_step"]) / d["value"] < 1e-3
+            for k in ("roofline", "cpu_baseline", "parity_check", "vendor_comparator", "varlen_padded_comparator", "measured_ceiling_8k_cubed", "clock",
+                      "hbm_segments", "other_configs"):
+                assert d[k] is None, k
+            assert d["step_launch"]["steps_by_method"] == {"eager": 3}
+            out = {n[:-4]: np.load(os.path.join(tmp, str(i), n)) for n in sorted(os.listdir(os.path.join(tmp, str(i))))}
+            assert set(out) == {"loss", "image_feat", "parallel_audio_feat"}, sorted(out)
+            assert out["loss"].dtype == np.float64 and abs(out["loss"][0] - d["loss"]) < 1e-4
+            for k in ("image_feat", "parallel_audio_feat"):
+                assert out[k].dtype == np.float32 and out[k].shape == (8, 512) and np.allclose(np.linalg.norm(out[k], axis=1), 1, atol=1e-2)
+            runs.append(out)
+        for k in runs[0]:
+            assert np.allclose(runs[0][k], runs[1][k], rtol=0, atol=1e-3), k
+        t = _run("--train", "--dump-outputs", os.path.join(tmp, "train"), steps=2, full=False)
+        assert t["config"]["mode"].startswith("train") and t["roofline"] is None
+        lt = np.load(os.path.join(tmp, "train", "loss.npy"))
+        assert lt.dtype == np.float64 and abs(lt[0] - t["loss"]) < 1e-4 and np.load(os.path.join(tmp, "train", "image_feat.npy")).shape == (8, 512)

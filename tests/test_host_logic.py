@@ -825,7 +825,24 @@ def test_bench_gpus2_self_launches_and_runs_under_torchrun_dry_run():
     assert r.returncode != 0 and "WORLD_SIZE=2" in (r.stderr + r.stdout)
 
 
-@pytest.mark.skipif(not os.path.isdir("/root/reference/config/speechCLIP"), reason="needs the reference's YAML files (build container only)")
+def test_bench_dump_outputs_dry_run(tmp_path):
+    """`bench.py --dump-outputs DIR` writes the last timed step's loss and loss features as .npy; `--steps` is the number of timed steps, and the
+    seeded inputs make two runs with the same arguments write the same arrays (CPU/gloo dry run, two ranks: rank 0 writes the global batch)."""
+    import sys
+    bench = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "bench.py")
+    outs = []
+    for i in range(2):
+        d = _bench_line([sys.executable, bench, "--gpus", "2", "--dry-run", "--steps", "4", "--warmup", "1", "--batch", "4",
+                         "--dump-outputs", str(tmp_path / str(i))])
+        assert d["steps"] == 4 and d["ms_per_step"] > 0
+        outs.append({n[:-4]: np.load(tmp_path / str(i) / n) for n in sorted(os.listdir(tmp_path / str(i)))})
+    assert set(outs[0]) == {"loss", "image_feat", "parallel_audio_feat"}
+    assert outs[0]["loss"].dtype == np.float64 and abs(outs[0]["loss"][0] - d["loss"]) < 1e-4
+    assert outs[0]["image_feat"].dtype == np.float32 and outs[0]["image_feat"].shape == (8, 512)
+    for k in outs[0]:
+        assert np.array_equal(outs[0][k], outs[1][k]), k
+
+
 @pytest.mark.parametrize("rel", ["model_base/spchclp_p.yaml", "model_base/spchclp_c.yaml", "model_large/flickr/spchclp_p.yaml",
                                  "model_large/flickr/spchclp_c.yaml", "model_large/coco/spchclp_p.yaml", "model_large/coco/spchclp_c.yaml"])
 def test_reference_yaml_builds_through_the_task_entry_point(rel, tmp_path, monkeypatch):
@@ -835,7 +852,7 @@ def test_reference_yaml_builds_through_the_task_entry_point(rel, tmp_path, monke
     import argparse
     import yaml
     import avssl.task as task_mod                                  # the alias package, as run_task.py imports it
-    path = os.path.join("/root/reference/config/speechCLIP", rel)
+    path = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "speechclip_configs", rel)   # the shipped files, verbatim
     cfg = yaml.load(open(path), Loader=yaml.FullLoader)
     vocab_file = cfg["clip"].get("reduce_subword_embbedding")
     if vocab_file:                                                 # relative path in the YAML (spchclp_c.yaml:94): provide the file there

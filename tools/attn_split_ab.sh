@@ -11,7 +11,7 @@ for l in sys.stdin:
         d=json.loads(l); print('$tag', d['ms_per_step'], d.get('clock',{}).get('sclk_mhz_under_load'), d.get('loss'))
 " >> $O/ab.log
 }
-COMMON="--steps 10 --warmup 3 --no-other-configs --cpu-pairs 0 --no-vendor-comparator"
+COMMON="--full --steps 10 --warmup 3 --no-other-configs --cpu-pairs 0 --no-vendor-comparator"
 for i in 1 2 3; do
   for cfg in "train --train" "large --model large" "varlen --varlen" "base"; do
     set -- $cfg; n=$1; shift

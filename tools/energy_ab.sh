@@ -8,7 +8,7 @@ export SPEECHCLIP_HIP_LIB=$R/speechclip_amd/libspeechclip_hip_probes.so
 P=${1:-2}
 run() {  # label, env assignments...
     local label=$1; shift
-    env "$@" python $R/bench.py --steps 20 --warmup 5 --cpu-pairs 0 --no-vendor-comparator --no-other-configs --no-roofline-events 2>/dev/null | python -c "
+    env "$@" python $R/bench.py --full --steps 20 --warmup 5 --cpu-pairs 0 --no-vendor-comparator --no-other-configs --no-roofline-events 2>/dev/null | python -c "
 import sys, json
 d = json.loads(sys.stdin.read()); c = d['clock'] or {}
 print('%-34s %8.3f ms/step %8.1f pairs/s  sclk %5s MHz  %7s W  %6s J/step' % ('$label', d['ms_per_step'], d['value'], c.get('sclk_mhz_under_load'), c.get('socket_power_w'), c.get('joules_per_step')))"

@@ -4,7 +4,7 @@ R=$GRAFT_REPO_ROOT; O=$R/gpurun_out/vithead; mkdir -p $O; cd $R
 for i in 1 2 3; do
   for m in "" head layer10; do
     for cfg in "cascaded" "base"; do
-      SC_VIT_START=$m timeout 300 python bench.py --model $cfg --steps 10 --warmup 3 --no-other-configs --cpu-pairs 0 --no-vendor-comparator 2>/dev/null | python -c "
+      SC_VIT_START=$m timeout 300 python bench.py --full --model $cfg --steps 10 --warmup 3 --no-other-configs --cpu-pairs 0 --no-vendor-comparator 2>/dev/null | python -c "
 import sys,json
 for l in sys.stdin:
     if l.startswith('{'):
