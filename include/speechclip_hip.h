@@ -155,6 +155,17 @@ int sc_dropout_add_layernorm_bf16(const void* x, const void* residual, const flo
 int sc_cls_attention_fwd(const void* cls_qkv, const void* kv_x, int64_t ld_kv, const int32_t* lens, void* out, int B, int T,
                          int NQ, int H, int head_dim, float scale, void* stream);
 
+/* Flash-style forward for head_dim 64 / 96 / 128 (MFMA): the full-row layers of a parallel branch with n_layers >= 2 (8 heads: head_dim 96 at
+ * d = 768, 128 at d = 1024) and the per-utterance CLS row of its last layer (Tq = 1).  Sequence b has Tq query rows and Tk key rows; klens[b]
+ * keys are valid (NULL = Tk).  Element (b, t, h, e) of q is at q[b*q_bs + t*q_rs + h*head_dim + e], of k / v at b*kv_bs + t*kv_rs + ..., of
+ * out at b*o_bs + t*o_rs + ... (elements).  bf16 q / k / v; out bf16, or fp32 with SC_ATTN_HD_OUT_F32.  fp32 scores / softmax.  drop_p > 0:
+ * dropout on the probabilities with sc_attention_fwd_dropout's mask (pair index ((b*H + h)*Tk + t) * ceil(Tk / 2) + key / 2).
+ * Other head dims return an error: sc_attention_fwd keeps its head_dim-64 contract. */
+#define SC_ATTN_HD_OUT_F32 0x10
+int sc_attention_hd_fwd(const void* q, const void* k, const void* v, void* out, const int32_t* klens, int B, int H, int Tq, int Tk,
+                        int head_dim, int64_t q_bs, int64_t q_rs, int64_t kv_bs, int64_t kv_rs, int64_t o_bs, int64_t o_rs,
+                        float scale, float drop_p, uint32_t seed, int flags, void* stream);
+
 /* Full-row multi-head attention, any head_dim <= 1024 (multiple of 8), arbitrary boolean key-padding mask (uint8 [B, L], 1 = padding;
  * NULL = none): torch.nn.MultiheadAttention(batch_first) as the reference's pooling heads call it on WHOLE sequences --
  * TransformerEncoder.forward / extract_hidden_states (avssl/module/kw_modules/TransformerModels.py:77-96) and

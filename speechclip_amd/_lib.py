@@ -17,6 +17,7 @@ ACT_NONE, ACT_GELU, ACT_QUICKGELU = 0, 1, 2
 GEMM_OUT_F32 = 0x10
 GEMM_F16 = 0x20          # SC_GEMM_F16: IEEE-half operands (and 16-bit outputs)
 ATTN_CAUSAL, ATTN_F16 = 0x1, 0x2
+ATTN_HD_OUT_F32 = 0x10
 
 _lib = None
 
@@ -75,6 +76,7 @@ def _declare(L):
         "sc_wave_layernorm": ([P, P, P, I, L64, F, P], c_int),
         "sc_attention_fwd": ([P, P, P, P, P, I, I, I, I, L64, L64, F, I, P], c_int),
         "sc_attention_fwd_dropout": ([P, P, P, P, P, I, I, I, I, L64, L64, F, I, F, U32, P], c_int),
+        "sc_attention_hd_fwd": ([P, P, P, P, P, I, I, I, I, I, L64, L64, L64, L64, L64, L64, F, F, U32, I, P], c_int),
         "sc_dropout_bf16": ([P, P, P, L64, F, U32, P], c_int),
         "sc_dropout_add_layernorm_bf16": ([P, P, P, P, P, L64, I, F, F, U32, P], c_int),
         "sc_cls_attention_fwd": ([P, P, L64, P, P, I, I, I, I, I, F, P], c_int),

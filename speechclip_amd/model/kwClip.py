@@ -293,9 +293,12 @@ class KW_ParallelBranch(nn.Module):
         return _branch_hidden_states(self, audio_feat, audio_len, 1)
 
     def forward(self, audio_feat: torch.Tensor, audio_len: torch.Tensor) -> torch.Tensor:
-        if torch.is_grad_enabled() and self.cls.requires_grad:
+        # a stacked branch (n_layers >= 2 or norm_first) has no differentiable path yet: in eval() mode it runs the forward without gradients
+        # instead of refusing; in train() mode _forward_train raises
+        stacked_eval = getattr(self.self_att, "stacked", False) and not self.training
+        if torch.is_grad_enabled() and self.cls.requires_grad and not stacked_eval:
             return self._forward_train(audio_feat, audio_len)
-        out = self.self_att.forward_cls(self.cls, audio_feat, audio_len)            # f32 [B, d] (bf16 with SC_HEAD_PRECISE=0)
+        out = self.self_att.forward_cls(self.cls, audio_feat, audio_len)            # f32 [B, d] (bf16 with SC_HEAD_PRECISE=0, one-layer head only)
         if hasattr(self, "linear_proj"):
             if out.dtype == torch.float32:
                 out = TransformerModels.hp_linear(out, self.linear_proj.weight, self.linear_proj.bias)
@@ -318,6 +321,9 @@ def _branch_hidden_states(branch, audio_feat: torch.Tensor, audio_len: torch.Ten
 def _kw_parallel_forward_train(self, audio_feat: torch.Tensor, audio_len: torch.Tensor) -> torch.Tensor:
     """Differentiable path (train_tail.ParallelBranchTrainFn): fp32 master weights, dropout active in train() mode."""
     from ..train_tail import ParallelBranchTrainFn
+    if getattr(self.self_att, "stacked", False):
+        raise NotImplementedError("parallel branch with n_layers >= 2 or norm_first: training is not implemented (the eval forward, validation "
+                                  "and extract_hidden_states run on the HIP kernels; the branch's backward is not built)")
     L = self.self_att.model.layers[0]
     sa = L.self_attn
     src = getattr(audio_feat, "_mix_src", None)

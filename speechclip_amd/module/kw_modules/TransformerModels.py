@@ -1,11 +1,12 @@
 """CLS-pooling heads (avssl/module/kw_modules/TransformerModels.py:48-135) on the HIP kernels.
 
-`TransformerEncoder` (parallel branch: 1 post-LN encoder layer + final LayerNorm) and
+`TransformerEncoder` (parallel branch: n post-LN or pre-LN encoder layers + final LayerNorm) and
 `MultiheadAttentionAndNorm` (cascaded branch: LN(MHA(x) + x)) keep the reference's constructor arguments and
 `state_dict` key names (`model.layers.0.self_attn.in_proj_weight`, `model.norm.*`,
 `multihead_attn_layer.*`, `attentionBlock_Norm.*`).  The reference evaluates every row of
 [CLS ; frames] and then keeps only the CLS rows (kwClip.py:1099, :879); here only the CLS rows are computed
-(`forward_cls`): K/V for all frames, Q / attention / FFN / LayerNorm for the NQ learned tokens only.
+(`forward_cls`): K/V for all frames, Q / attention / FFN / LayerNorm for the NQ learned tokens only.  A branch deeper than one layer (or
+pre-LN) runs layers 0..n-2 on every row of [CLS; frames] and the last layer on the CLS rows only (`_forward_cls_stack`).
 """
 import os
 import weakref
@@ -165,16 +166,27 @@ class TransformerEncoder(nn.Module):
     def __init__(self, n_layers: int = 1, d_model: int = 768, nhead: int = 8, dim_feedforward: int = 3072, dropout: float = 0.1,
                  activation: str = "gelu", layer_norm_eps: float = 1e-5, batch_first: bool = True, norm_first: bool = False) -> None:
         super().__init__()
-        if n_layers != 1 or norm_first or activation != "gelu" or not batch_first:
-            raise NotImplementedError("MI355X parallel branch supports the shipped shape: 1 post-LN GELU layer, batch_first")
-        self.nhead, self.eps = nhead, layer_norm_eps
+        if activation != "gelu" or not batch_first:
+            raise NotImplementedError("MI355X parallel branch supports GELU layers with batch_first=True")
+        if n_layers < 1:
+            raise ValueError(f"TransformerEncoder: n_layers={n_layers} must be >= 1")
+        # n_layers == 1 post-LN (the shipped shape) keeps the algebraic CLS-rows head; any other depth / order runs the stack
+        # (full-row layers 0..n-2 on sc_attention_hd_fwd, CLS rows of the last layer), which takes the head dims of that kernel
+        self.stacked = n_layers != 1 or norm_first
+        if self.stacked and (d_model % nhead or d_model // nhead not in ops.ATTN_HD_DIMS):
+            raise NotImplementedError(f"MI355X parallel branch with n_layers={n_layers}, norm_first={norm_first}: head_dim "
+                                      f"{d_model / nhead:g} (d_model {d_model} / nhead {nhead}) is not in the supported set {{64, 96, 128}}")
+        self.nhead, self.eps, self.n_layers, self.norm_first = nhead, layer_norm_eps, n_layers, norm_first
         self.model = _EncoderStack(dict(d_model=d_model, nhead=nhead, dim_feedforward=dim_feedforward, dropout=dropout,
                                         activation=activation, layer_norm_eps=layer_norm_eps, batch_first=batch_first,
                                         norm_first=norm_first), n_layers, d_model)
 
     def forward_cls(self, cls: torch.Tensor, audio_feat: torch.Tensor, audio_len: torch.Tensor) -> torch.Tensor:
-        """cls [1,1,D]; audio_feat bf16 [B,T,D]; audio_len [B] (valid frames, without the CLS).  -> f32 [B, D] (bf16 with SC_HEAD_PRECISE=0):
-        row 0 of norm(layer([CLS; x])) -- what kwClip.py:1097-1099 keeps."""
+        """cls [1,1,D]; audio_feat bf16 [B,T,D]; audio_len [B] (valid frames, without the CLS).  -> f32 [B, D]: row 0 of norm(layers([CLS; x]))
+        -- what kwClip.py:1097-1099 keeps.  The one-layer post-LN head returns bf16 with SC_HEAD_PRECISE=0; the stack (`_forward_cls_stack`)
+        ignores SC_HEAD_PRECISE and always returns f32."""
+        if self.stacked:
+            return self._forward_cls_stack(cls, audio_feat, audio_len)
         L = self.model.layers[0]
         sa = L.self_attn
         D = cls.shape[-1]
@@ -200,18 +212,69 @@ class TransformerEncoder(nn.Module):
         x2 = ops.layernorm(y2, f32(L.norm2.weight), f32(L.norm2.bias), self.eps, out_f32=True)
         return ops.layernorm(x2, f32(self.model.norm.weight), f32(self.model.norm.bias), 1e-5)
 
+    # ---- stack path (n_layers >= 2 or norm_first): layers 0..n-2 on every row of [CLS; frames] (padded [B, T + 1, d] rows, key lengths
+    #      len + 1), then the last layer on the B CLS rows only: K / V of all rows, per-utterance CLS query.  Eval-mode arithmetic, no autograd.
+    @torch.no_grad()
+    def _forward_cls_stack(self, cls: torch.Tensor, audio_feat: torch.Tensor, audio_len: torch.Tensor) -> torch.Tensor:
+        """-> f32 [B, D]: row 0 of norm(layers([CLS; x])).  Precision of the CLS rows: the last layer's out-proj, FFN and LayerNorms are
+        fp32-grade (hp_linear), as in the one-layer head; its attention is bf16-grade -- query rounded to bf16, K / V from the bf16 GEMM, bf16
+        probabilities into the MFMA, fp32 softmax and accumulation.  The one-layer head keeps the pooled value sums at fp32 grade; here the
+        frames reaching the last layer have already been through bf16 full-row layers, so that step would not make the row fp32-grade."""
+        B, T, D = audio_feat.shape
+        Lq = T + 1
+        x = torch.empty(B, Lq, D, device=audio_feat.device, dtype=torch.float32)
+        x[:, 0] = cls.detach().reshape(D)
+        x[:, 1:] = audio_feat.detach()
+        x = x.view(B * Lq, D)
+        klens = (audio_len.to(device=audio_feat.device, dtype=torch.int32) + 1).contiguous()
+        hd = D // self.nhead
+        attend = lambda qkv: ops.attention_hd_qkv(qkv, B, Lq, self.nhead, klens)   # noqa: E731
+        for i in range(self.n_layers - 1):
+            x = self._layer_rows(x, None, B, Lq, i, attend)
+        # last layer, CLS rows only, fp32-grade (hp_linear) like forward_cls: K / V of every row feed one query per utterance
+        L = self.model.layers[-1]
+        sa = L.self_attn
+        f32 = lambda t: cached_cast(t, torch.float32)  # noqa: E731
+        xc = x.view(B, Lq, D)[:, 0].contiguous()
+        if self.norm_first:
+            a_all = ops.layernorm(x, f32(L.norm1.weight), f32(L.norm1.bias), self.eps)
+            ac = ops.layernorm(xc, f32(L.norm1.weight), f32(L.norm1.bias), self.eps, out_f32=True)
+        else:
+            a_all, ac = x.to(BF), xc
+        kv = ops.gemm(a_all, cached_cast(sa.in_proj_weight, BF)[D:], f32(sa.in_proj_bias)[D:])              # bf16 [B*Lq, 2D] = k | v
+        qc = hp_linear(ac, sa.in_proj_weight, sa.in_proj_bias)[:, :D].to(BF).contiguous()                   # [B, D] (B rows: all of in_proj)
+        att = ops.attention_hd(qc, kv, kv[:, D:], B, self.nhead, 1, Lq, hd, (D, D), (Lq * 2 * D, 2 * D), klens, out_f32=True).view(B, D)
+        if self.norm_first:
+            x1 = hp_linear(att, sa.out_proj.weight, sa.out_proj.bias, residual=xc)
+            a2 = ops.layernorm(x1, f32(L.norm2.weight), f32(L.norm2.bias), self.eps, out_f32=True)
+            y = hp_linear(hp_linear(a2, L.linear1.weight, L.linear1.bias, ACT_GELU), L.linear2.weight, L.linear2.bias, residual=x1)
+        else:
+            y = hp_linear(att, sa.out_proj.weight, sa.out_proj.bias, residual=xc)
+            x1 = ops.layernorm(y, f32(L.norm1.weight), f32(L.norm1.bias), self.eps, out_f32=True)
+            y2 = hp_linear(hp_linear(x1, L.linear1.weight, L.linear1.bias, ACT_GELU), L.linear2.weight, L.linear2.bias, residual=x1)
+            y = ops.layernorm(y2, f32(L.norm2.weight), f32(L.norm2.bias), self.eps, out_f32=True)
+        return ops.layernorm(y, f32(self.model.norm.weight), f32(self.model.norm.bias), 1e-5, out_f32=True)
+
     # ---- full-row path (TransformerModels.py:77-96): every position of [CLS; frames], any boolean key-padding mask.  Off the hot path
     #      (forward_cls is what KW_ParallelBranch.forward runs); eval-mode arithmetic (no dropout), no autograd.
     @torch.no_grad()
-    def _layer_rows(self, x32: torch.Tensor, key_padding_mask, B: int, Lq: int) -> torch.Tensor:
-        """One post-LN nn.TransformerEncoderLayer on fp32 rows [B*L, D] -> fp32 rows."""
-        L = self.model.layers[0]
+    def _layer_rows(self, x32: torch.Tensor, key_padding_mask, B: int, Lq: int, i: int = 0, attend=None) -> torch.Tensor:
+        """nn.TransformerEncoderLayer i (post-LN, or pre-LN with norm_first) on fp32 rows [B*L, D] -> fp32 rows.  `attend(qkv)` -> bf16 [B*L, D]
+        (default: attention_rows with the boolean key-padding mask)."""
+        L = self.model.layers[i]
         sa = L.self_attn
         D = x32.shape[-1]
         f32 = lambda t: cached_cast(t, torch.float32)  # noqa: E731
         w16 = lambda t: cached_cast(t, BF)             # noqa: E731
+        if attend is None:
+            attend = lambda qkv: ops.attention_rows(qkv, B, Lq, self.nhead, D // self.nhead, key_padding_mask)   # noqa: E731
+        if self.norm_first:         # x + SA(LN1(x)), then + FF(LN2(.))
+            qkv = ops.gemm(ops.layernorm(x32, f32(L.norm1.weight), f32(L.norm1.bias), self.eps), w16(sa.in_proj_weight), f32(sa.in_proj_bias))
+            x1 = ops.gemm(attend(qkv), w16(sa.out_proj.weight), f32(sa.out_proj.bias), residual=x32, out_f32=True)
+            h = ops.gemm(ops.layernorm(x1, f32(L.norm2.weight), f32(L.norm2.bias), self.eps), w16(L.linear1.weight), f32(L.linear1.bias), ACT_GELU)
+            return ops.gemm(h, w16(L.linear2.weight), f32(L.linear2.bias), residual=x1, out_f32=True)
         qkv = ops.gemm(x32.to(BF), w16(sa.in_proj_weight), f32(sa.in_proj_bias))
-        att = ops.attention_rows(qkv, B, Lq, self.nhead, D // self.nhead, key_padding_mask)
+        att = attend(qkv)
         y = ops.gemm(att, w16(sa.out_proj.weight), f32(sa.out_proj.bias), residual=x32, out_f32=True)
         x1 = ops.layernorm(y, f32(L.norm1.weight), f32(L.norm1.bias), self.eps, out_f32=True)
         h = ops.gemm(x1.to(BF), w16(L.linear1.weight), f32(L.linear1.bias), ACT_GELU)
@@ -229,8 +292,9 @@ class TransformerEncoder(nn.Module):
         B, Lq, D = src.shape
         x = src.detach().float().contiguous().view(B * Lq, D)
         hidden = [x.view(B, Lq, D)]
-        x = self._layer_rows(x, key_padding_mask, B, Lq)
-        hidden.append(x.view(B, Lq, D))
+        for i in range(len(self.model.layers)):
+            x = self._layer_rows(x, key_padding_mask, B, Lq, i)
+            hidden.append(x.view(B, Lq, D))
         out = ops.layernorm(x, cached_cast(self.model.norm.weight, torch.float32), cached_cast(self.model.norm.bias, torch.float32), 1e-5, out_f32=True)
         return out.view(B, Lq, D), tuple(hidden)
 

@@ -8,7 +8,7 @@ from typing import Optional
 import torch
 
 from . import _lib
-from ._lib import ACT_GELU, ACT_NONE, ACT_QUICKGELU, ATTN_CAUSAL, ATTN_F16, GEMM_F16, GEMM_OUT_F32, check, lib, ptr, stream
+from ._lib import ACT_GELU, ACT_NONE, ACT_QUICKGELU, ATTN_CAUSAL, ATTN_F16, ATTN_HD_OUT_F32, GEMM_F16, GEMM_OUT_F32, check, lib, ptr, stream
 
 bf16 = torch.bfloat16
 
@@ -281,6 +281,34 @@ def dropout_add_layernorm(x, residual, gamma, beta, drop_p, seed, eps=1e-5, out=
         return layernorm(x, gamma, beta, eps, out=out)
     check(rc, "sc_dropout_add_layernorm_bf16")
     return out
+
+
+ATTN_HD_DIMS = (64, 96, 128)
+
+
+def attention_hd(q, k, v, B, H, Tq, Tk, hd, q_strides, kv_strides, klens_i32=None, out=None, out_f32=False, scale=None, drop_p=0.0, seed=0):
+    """Flash attention for head_dim 64 / 96 / 128 (sc_attention_hd_fwd).  q / k / v: bf16 views whose data_ptr is element (b 0, row 0, head 0);
+    `q_strides` / `kv_strides` = (per-sequence, per-row) element strides.  Returns out [B, Tq, H*hd] (bf16, or f32 with out_f32); klens_i32 [B]
+    valid keys per sequence (None = Tk); drop_p > 0: dropout on the probabilities (sc_attention_fwd_dropout's mask)."""
+    _need_cuda(q, k, v)
+    assert q.dtype == bf16 and k.dtype == bf16 and v.dtype == bf16
+    D = H * hd
+    if out is None:
+        out = torch.empty(B, Tq, D, device=q.device, dtype=torch.float32 if out_f32 else bf16)
+    assert out.dtype == (torch.float32 if out_f32 else bf16) and out.is_contiguous() and out.numel() == B * Tq * D
+    check(lib().sc_attention_hd_fwd(ptr(q), ptr(k), ptr(v), ptr(out), ptr(klens_i32), B, H, Tq, Tk, hd, q_strides[0], q_strides[1],
+                                    kv_strides[0], kv_strides[1], Tq * D, D, hd ** -0.5 if scale is None else scale, float(drop_p),
+                                    int(seed) & 0xffffffff, ATTN_HD_OUT_F32 if out_f32 else 0, stream()), "sc_attention_hd_fwd")
+    return out
+
+
+def attention_hd_qkv(qkv, B, L, H, klens_i32=None, out_f32=False, drop_p=0.0, seed=0):
+    """Full-row attention over packed rows qkv [B*L, 3*D] (q | k | v, D = H * head_dim) -> [B*L, D]."""
+    assert qkv.dim() == 2 and qkv.is_contiguous() and qkv.shape[0] == B * L and qkv.shape[1] % (3 * H) == 0
+    D = qkv.shape[1] // 3
+    s = (L * 3 * D, 3 * D)
+    out = attention_hd(qkv, qkv[:, D:], qkv[:, 2 * D:], B, H, L, L, D // H, s, s, klens_i32, out_f32=out_f32, drop_p=drop_p, seed=seed)
+    return out.view(B * L, D)
 
 
 def attention_rows(qkv, B, L, H, hd, key_padding_mask=None, scale=None):
