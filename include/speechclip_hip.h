@@ -423,6 +423,24 @@ int sc_attention_fwd_packed(const void* q, const void* k, const void* v, void* o
                             int flags /* SC_ATTN_F16 or 0 */, void* stream);
 int sc_unpack_rows(const void* src, int64_t src_layer_stride_bytes, const int32_t* row_off, void* out, int64_t out_layer_stride_bytes, int n_layers,
                    int B, int T_out, int row_bytes, int halo, void* stream);
+/* sc_pack_rows: padded [n_layers][B][T_in][row] -> packed, the adjoint of sc_unpack_rows: out[l][row_off[b] + t] = t < min(rows_b - halo, T_in) ? in[l][b][t] : 0
+ * for every row of every utterance (row_off[B] == total_rows). */
+int sc_pack_rows(const void* src, int64_t src_layer_stride_bytes, const int32_t* row_off, void* out, int64_t out_layer_stride_bytes, int n_layers,
+                 int B, int T_in, int64_t total_rows, int row_bytes, int halo, void* stream);
+
+/* ---- Fused attention backward over packed rows (fine-tuning on the padding-free layout), head_dim 64.  Operands as sc_attention_fwd_packed: bf16 rows,
+ * head h at column h*64, utterance b at rows row_off[b] .. (row_off[B] == total_rows; rows per utterance <= Tmax), klens[b] valid keys; row_off == NULL:
+ * the uniform layout row_off[b] = b*Tmax (total_rows = B*Tmax).  O / dO: the forward's output and its gradient (row stride ld_o); dq / dk / dv: row stride
+ * ld_dqkv.  Flash-style: S = Q K^T and dP = dO V^T are recomputed on the MFMA in a key-tile-stationary sweep (dK, dV) and a query-tile-stationary sweep (dQ);
+ * nothing of size L x L is written.  `workspace` (sc_attention_bwd_packed_workspace_bytes: 2 fp32 per (row, head)) receives the log-sum-exp and
+ * delta = dO . O of a pre-pass.  No atomics: results are bitwise reproducible.  drop_p > 0: the forward ran with (drop_p, seed); its mask is regenerated
+ * (P for dV is the dropped, rescaled one, dP is masked before the softmax backward: sc_attn_softmax_bwd_dropout's semantics).
+ * Query rows >= klens[b] of an utterance take no part: dq = 0 there and they add nothing to dk / dv; key rows >= klens[b] get dk = dv = 0.  Every row
+ * in [0, total_rows) of dq / dk / dv is written. */
+int64_t sc_attention_bwd_packed_workspace_bytes(int64_t total_rows, int H);
+int sc_attention_bwd_packed(const void* q, const void* k, const void* v, int64_t ld_qkv, const void* O, const void* dO, int64_t ld_o,
+                            const int32_t* klens, const int32_t* row_off, int B, int H, int Tmax, int64_t total_rows, int head_dim, float scale,
+                            float drop_p, uint32_t seed, void* dq, void* dk, void* dv, int64_t ld_dqkv, void* workspace, void* stream);
 #ifdef __cplusplus
 }
 #endif

@@ -529,6 +529,45 @@ extern "C" int sc_unpack_rows(const void* src, int64_t src_layer_stride_bytes, c
 }
 
 
+// Padded -> packed: the adjoint of sc_unpack_rows (its backward at the encoder / head boundary).  out[l][row_off[b] + t][:] = in[l][b][t][:] for
+// t < min(rows_b - halo, T_in), zeros on the other rows of the utterance (the halo row among them).  One wave per packed row; the utterance of a row
+// is found by bisection of row_off.
+__global__ __launch_bounds__(256) void pack_rows_kernel(const char* __restrict__ src, int64_t src_layer_stride, const int32_t* __restrict__ row_off,
+                                                        char* __restrict__ out, int64_t out_layer_stride, int B, int T_in, int64_t total_rows,
+                                                        int row_bytes, int halo) {
+    const int lane = threadIdx.x & 63;
+    const int64_t r = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (r >= total_rows) return;
+    int lo = 0, hi = B;                       // largest b with row_off[b] <= r
+    while (hi - lo > 1) {
+        const int mid = (lo + hi) >> 1;
+        if ((int64_t)row_off[mid] <= r) lo = mid; else hi = mid;
+    }
+    const int b = lo, t = (int)(r - row_off[b]);
+    const int l = blockIdx.y;
+    const int rows_b = row_off[b + 1] - row_off[b] - halo;
+    const bool live = t < rows_b && t < T_in;      // (rows at or beyond row_off[B] are zero-filled too)
+    const char* s = src + l * src_layer_stride + ((int64_t)b * T_in + (live ? t : 0)) * row_bytes;
+    char* o = out + l * out_layer_stride + r * row_bytes;
+    for (int c = lane * 16; c < row_bytes; c += 64 * 16) {
+        uint4 v = make_uint4(0, 0, 0, 0);
+        if (live) v = *(const uint4*)(s + c);
+        *(uint4*)(o + c) = v;
+    }
+}
+
+extern "C" int sc_pack_rows(const void* src, int64_t src_layer_stride_bytes, const int32_t* row_off, void* out, int64_t out_layer_stride_bytes, int n_layers,
+                            int B, int T_in, int64_t total_rows, int row_bytes, int halo, void* stream) {
+    SC_CHECK_ARG(src && row_off && out && n_layers >= 1 && n_layers <= 65535 && row_bytes > 0 && row_bytes % 16 == 0 && halo >= 0, "sc_pack_rows: bad arguments (row_bytes must be a multiple of 16)");
+    if (B <= 0 || T_in <= 0 || total_rows <= 0) return 0;
+    SC_CHECK_ARG((total_rows + 3) / 4 < 0x7fffffffLL, "sc_pack_rows: too many rows");
+    hipLaunchKernelGGL(pack_rows_kernel, dim3((unsigned)((total_rows + 3) / 4), n_layers), dim3(256), 0, (hipStream_t)stream, (const char*)src, src_layer_stride_bytes,
+                       row_off, (char*)out, out_layer_stride_bytes, B, T_in, total_rows, row_bytes, halo);
+    SC_CHECK_LAUNCH();
+    return 0;
+}
+
+
 // `normalize_hiddenstates` with `normalize_type` method1 / method2 (speech_encoder_plus.py:572-592), IN PLACE on the stacked hidden states
 // x = [n_layers][B][Tp][D] (bf16 post-LN / f32 pre-LN residual stream), as the reference overwrites `layer_results[i]`:
 //   method1: row /= (||row||_2 + 1e-8)          method2: row /= mean_{t < T} ||x[i, b, t, :]||_2   (ALL T frames of the padded batch, padded frames included)

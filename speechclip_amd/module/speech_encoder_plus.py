@@ -322,6 +322,12 @@ def _forward_finetune(self, padded, lens, feat_select_idx, return_hidden_states,
             h_front = HubertFrontTrainFn.apply(fmeta, padded.contiguous(), valid_dev, *front_params(enc))      # [B*Tp, d]
         hidden = None
     else:
+        # Padding-free fine-tuning: the frozen layers below L0, the trained layers and the layer mix all run on sum_b rows_b packed rows; the reference's
+        # [B, T, d] layout is restored at the boundary only.  Same SC_VARLEN_PACK=0|1|auto rule as the frozen forward (`_pack_plan`).  Whole-encoder training
+        # (train_front) stays padded.
+        pack = self._pack_plan(padded, lens)
+        if pack is not None:
+            return self._forward_finetune_packed(padded, lens, return_hidden_states, drop_seed, pack)
         # (train-mode dropouts: the frozen layers below L0 through the engine, the trained nodes through their own masks)
         hidden, T, Tp, valid = enc.extract_all_layers(padded, lens, stop_layer=L0, dropout_seed=drop_seed)        # hidden[0 .. L0] are valid
     M = B * Tp
@@ -349,6 +355,44 @@ def _forward_finetune(self, padded, lens, feat_select_idx, return_hidden_states,
 
 
 FairseqSpeechEncoder_Hubert._forward_finetune = _forward_finetune
+
+
+def _forward_finetune_packed(self, padded, lens, return_hidden_states, drop_seed, pack):
+    """_forward_finetune over packed rows (pack = packed_geometry): utterance b owns rows pack["row_off"][b] .. of every tensor.  The attention of the trained
+    layers runs on sc_attention_fwd_packed / sc_attention_bwd_packed; the mixed frames go back to [B, T, d] through a differentiable unpack (forward
+    sc_unpack_rows with halo = 1, backward sc_pack_rows), so the heads see what the frozen packed path hands them."""
+    from ..train_hubert import HubertLayersTrainFn, UnpackRowsFn, WeightedSumTrainFn, layer_params
+    enc = self.encoder
+    cfg = enc.cfg
+    dev = padded.device
+    L0, nl = self.train_layers[0], cfg.encoder_layers
+    B, d = padded.shape[0], cfg.encoder_embed_dim
+    hidden, T, _, valid = enc.extract_all_layers(padded, lens, stop_layer=L0, dropout_seed=drop_seed, pack=pack)      # [L0 + 1, total, d]
+    M = pack["total"]
+    off = ops.dev_ints(pack["row_off"], torch.int32, dev)
+    params = []
+    for i in range(L0, nl):
+        params += layer_params(enc.encoder.layers[i])
+    meta = dict(B=B, Tp=pack["rows_max"], H=cfg.encoder_attention_heads, eps=1e-5, train=[i in self.train_layers for i in range(L0, nl)],
+                pre_ln=bool(cfg.layer_norm_first), pack=dict(row_off=off, rows_max=pack["rows_max"], total=M))
+    if drop_seed is not None:
+        r = enc.dropout_rates()
+        meta["drop"] = dict(hidden=r["hidden"], attention=r["attention"], activation=r["activation"], seed=(int(drop_seed) * 2654435761 + 97) & 0x7fffffff)
+    h_in = hidden[L0].clone()                       # the engine's hidden buffer is a reused workspace
+    hi = HubertLayersTrainFn.apply(meta, h_in, ops.dev_ints(valid, torch.int32, dev), *params)      # [nl - L0, total, d]
+    hidden_all = torch.cat([hidden[:L0 + 1].detach(), hi], 0)                                        # [nl + 1, total, d]
+    ws = self.weightedsum_layer
+    mixed = UnpackRowsFn.apply(WeightedSumTrainFn.apply(hidden_all, ws.weights, ws.normalize_features), off, B, T, 1)          # [B, T, d]
+    states = ops.unpack_rows(hidden_all.detach(), off, B, T, halo=1)                                 # [nl + 1, B, T, d], zeros beyond each utterance
+    mixed._mix_src = (states, ws)                                                                     # the mix weights' gradient comes out of the head's backward
+    feat_len = ops.dev_ints([min(round(l / self.downsample_rate), T) for l in lens], torch.long, dev).clone()
+    out = [mixed, feat_len]
+    if return_hidden_states:       # as on the padded layout: views of hidden_all, attached to the trained layers' autograd node
+        out.append(tuple(UnpackRowsFn.apply(hidden_all[i], off, B, T, 1) for i in range(nl + 1)))
+    return tuple(out)
+
+
+FairseqSpeechEncoder_Hubert._forward_finetune_packed = _forward_finetune_packed
 
 
 class S3prlSpeechEncoderPlus(nn.Module):

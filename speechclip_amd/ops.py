@@ -498,6 +498,41 @@ def unpack_rows(src, row_off_i32, B, T_out, halo=0):
     return out if three else out[0]
 
 
+def pack_rows(src, row_off_i32, total_rows, halo=0):
+    """The adjoint of unpack_rows: src [n, B, T, D] or [B, T, D] (padded) -> [n, total_rows, D] / [total_rows, D]; packed row t of utterance b takes
+    src[b, t] for t < min(rows_b - halo, T) and zeros otherwise."""
+    _need_cuda(src, row_off_i32)
+    four = src.dim() == 4
+    s4 = src if four else src.unsqueeze(0)
+    n, B, T, D = s4.shape
+    assert s4.is_contiguous() and (D * s4.element_size()) % 16 == 0 and row_off_i32.numel() == B + 1
+    out = torch.empty(n, int(total_rows), D, device=src.device, dtype=src.dtype)
+    rb = D * s4.element_size()
+    check(lib().sc_pack_rows(ptr(s4), B * T * rb, ptr(row_off_i32), ptr(out), int(total_rows) * rb, n, B, T, int(total_rows), rb, int(halo), stream()), "sc_pack_rows")
+    return out if four else out[0]
+
+
+def attention_bwd_packed(qkv, att, datt, B, rows_max, H, klens_i32, row_off_i32=None, drop=None, out=None):
+    """Fused attention backward (sc_attention_bwd_packed): qkv bf16 [total_rows, 3*H*64] (q | k | v), att / datt bf16 [total_rows, H*64] (the forward's
+    output and its gradient) -> dqkv bf16 [total_rows, 3*H*64].  row_off_i32 None: the uniform layout (total_rows = B * rows_max).  drop = (p, seed) of a
+    forward that ran with attention dropout.  The only temporary is the fp32 statistics workspace (2 floats per row and head)."""
+    _need_cuda(qkv, att, datt, klens_i32)
+    D = H * 64
+    total = att.shape[0]
+    assert qkv.dtype == bf16 and att.dtype == bf16 and datt.dtype == bf16
+    assert qkv.shape[0] >= total and qkv.shape[1] == 3 * D and att.shape == (total, D) and datt.shape == (total, D)
+    assert qkv.is_contiguous() and att.is_contiguous() and datt.is_contiguous()
+    if out is None:
+        out = torch.empty(total, 3 * D, device=qkv.device, dtype=bf16)
+    assert out.shape == (total, 3 * D) and out.is_contiguous() and out.dtype == bf16
+    ws = torch.empty(lib().sc_attention_bwd_packed_workspace_bytes(total, H), device=qkv.device, dtype=torch.uint8)
+    p_, seed = (float(drop[0]), int(drop[1]) & 0xffffffff) if drop is not None else (0.0, 0)
+    check(lib().sc_attention_bwd_packed(qkv.data_ptr(), qkv.data_ptr() + D * 2, qkv.data_ptr() + 2 * D * 2, 3 * D, ptr(att), ptr(datt), D, ptr(klens_i32),
+                                        ptr(row_off_i32), B, H, int(rows_max), total, 64, 0.125, p_, seed, out.data_ptr(), out.data_ptr() + D * 2,
+                                        out.data_ptr() + 2 * D * 2, 3 * D, ptr(ws), stream()), "sc_attention_bwd_packed")
+    return out
+
+
 _DEV_INTS = {}
 
 

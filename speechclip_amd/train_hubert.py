@@ -96,17 +96,74 @@ def attention_bwd(qkv: torch.Tensor, att: torch.Tensor, datt: torch.Tensor, B: i
     return dqkv
 
 
+def attention_bwd_packed(qkv: torch.Tensor, att: torch.Tensor, datt: torch.Tensor, B: int, rows_max: int, H: int, klens_i32: torch.Tensor,
+                         row_off_i32: torch.Tensor = None, drop=None) -> torch.Tensor:
+    """attention_bwd on the fused kernel (sc_attention_bwd_packed): qkv bf16 [total, 3*H*64], att / datt bf16 [total, H*64] over packed rows (utterance b at
+    rows row_off[b] .., at most rows_max each; row_off_i32 None: the uniform layout, total = B * rows_max) -> dqkv bf16 [total, 3*H*64].  S and dP are
+    recomputed per tile on the MFMA: no P / dS image, no transposed copies, no slack rows; the only temporary is 2 fp32 per (row, head)."""
+    return ops.attention_bwd_packed(qkv, att, datt, B, rows_max, H, klens_i32, row_off_i32, drop)
+
+
+def _pack_of(meta, dev):
+    """(row_off device ints, rows_max) of a packed batch (meta["pack"]), or None for the padded layout."""
+    pk = meta.get("pack")
+    if pk is None:
+        return None
+    off = pk["row_off"]
+    return (off if torch.is_tensor(off) else ops.dev_ints(off, torch.int32, dev)), int(pk["rows_max"])
+
+
+def _qkv_rows(pk, M, Lp, Tp, d, dev):
+    """The q | k | v buffer of one layer: M rows, plus zeroed slack rows on the padded layout (the image form of the backward reads Lp keys per utterance)."""
+    if pk is not None:
+        return torch.empty(M, 3 * d, device=dev, dtype=BF)
+    qkv = torch.empty(M + (Lp - Tp), 3 * d, device=dev, dtype=BF)
+    qkv[M:].zero_()          # slack rows: the backward's S / dP products read Lp keys per utterance
+    return qkv
+
+
+def _attn_fwd(pk, qkv, M, B, Tp, H, valid_i32, drop=None):
+    """drop = (p, seed): the train-mode form (dropout on the attention probabilities)."""
+    if pk is not None:
+        return ops.attention_packed(qkv, B, pk[1], H, valid_i32, pk[0], drop_p=drop[0] if drop else 0.0, seed=drop[1] if drop else 0)
+    if drop is not None:
+        return ops.attention_dropout(qkv[:M], B, Tp, H, valid_i32, drop[0], drop[1])
+    return ops.attention(qkv[:M], B, Tp, H, valid_i32)
+
+
+def _attn_bwd(pk, qkv, att, datt, B, Tp, H, valid_i32, drop=None):
+    if pk is not None:
+        return attention_bwd_packed(qkv, att, datt, B, pk[1], H, valid_i32, pk[0], drop)
+    return attention_bwd(qkv, att, datt, B, Tp, H, valid_i32, drop)
+
+
+class UnpackRowsFn(torch.autograd.Function):
+    """packed [total, D] -> the reference's padded [B, T, D] (sc_unpack_rows, halo row and rows beyond an utterance zero); backward: its adjoint sc_pack_rows."""
+
+    @staticmethod
+    def forward(ctx, x, row_off_i32, B, T, halo):
+        ctx.off, ctx.total, ctx.halo = row_off_i32, x.shape[0], int(halo)
+        return ops.unpack_rows(x.detach().contiguous(), row_off_i32, B, T, halo=halo)
+
+    @staticmethod
+    def backward(ctx, dy):
+        return ops.pack_rows(dy.contiguous(), ctx.off, ctx.total, halo=ctx.halo), None, None, None, None
+
+
 class HubertLayersTrainFn(torch.autograd.Function):
     """hidden bf16 [n, M, d] = outputs of post-LN layers L0 .. L0+n-1 applied to h_in.
-    args: meta (B, Tp, H, eps, train (list of bool per layer: compute parameter gradients)), h_in bf16 [M, d], valid_i32 [B], then 16 tensors per layer."""
+    args: meta (B, Tp, H, eps, train (list of bool per layer: compute parameter gradients)), h_in bf16 [M, d], valid_i32 [B], then 16 tensors per layer.
+    meta["pack"] = dict(row_off, rows_max, total): the padding-free layout -- M = total rows, utterance b at rows row_off[b] .., Tp = rows_max; attention runs
+    on ops.attention_packed forward and on the fused sc_attention_bwd_packed backward (every other kernel of a layer is row-wise)."""
 
     @staticmethod
     def forward(ctx, meta, h_in, valid_i32, *params):
         B, Tp, H, eps = meta["B"], meta["Tp"], meta["H"], meta["eps"]
         n = len(params) // PER_LAYER
         M, d = h_in.shape
-        assert M == B * Tp and d == H * 64
         dev = h_in.device
+        pk = _pack_of(meta, dev)         # packed rows: M = sum_b rows_b, Tp = the longest utterance's rows
+        assert (M == B * Tp if pk is None else M == meta["pack"]["total"]) and d == H * 64
         Lp = -(-Tp // 64) * 64
         pre_ln = bool(meta.get("pre_ln", False))
         if pre_ln:
@@ -124,18 +181,17 @@ class HubertLayersTrainFn(torch.autograd.Function):
         for li in range(n):
             qw, qb, kw, kb, vw, vb, ow, ob, g1, b1n, w1, b1, w2, b2, g2, b2n = params[li * PER_LAYER:(li + 1) * PER_LAYER]
             wqkv, bqkv = _w16(torch.cat([qw, kw, vw], 0)), _f32(torch.cat([qb, kb, vb], 0))
-            qkv = torch.empty(M + (Lp - Tp), 3 * d, device=dev, dtype=BF)
-            qkv[M:].zero_()          # slack rows: the backward's S / dP products read Lp keys per utterance
+            qkv = _qkv_rows(pk, M, Lp, Tp, d, dev)
             ops.gemm(h, wqkv, bqkv, out=qkv[:M])
             if drop is None:
-                att = ops.attention(qkv[:M], B, Tp, H, valid_i32)
+                att = _attn_fwd(pk, qkv, M, B, Tp, H, valid_i32)
                 y1 = ops.gemm(att, _w16(ow), _f32(ob), residual=h)
                 x1 = ops.layernorm(y1, _f32(g1), _f32(b1n), eps)
                 hm = ops.gemm(x1, _w16(w1), _f32(b1), ACT_GELU)
                 y2 = ops.gemm(hm, _w16(w2), _f32(b2), residual=x1)
             else:       # x = LN(x + dropout1(attn(x)));  x = LN(x + dropout3(fc2(dropout2(gelu(fc1 x)))))
                 sa, s1, s2, s3 = seeds[4 * li:4 * li + 4]
-                att = ops.attention_dropout(qkv[:M], B, Tp, H, valid_i32, drop["attention"], sa)
+                att = _attn_fwd(pk, qkv, M, B, Tp, H, valid_i32, (drop["attention"], sa))
                 y1 = ops.gemm(att, _w16(ow), _f32(ob))
                 ops.dropout_bf16(y1, drop["hidden"], s1, residual=h, out=y1)
                 x1 = ops.layernorm(y1, _f32(g1), _f32(b1n), eps)
@@ -161,6 +217,7 @@ class HubertLayersTrainFn(torch.autograd.Function):
         n = len(params) // PER_LAYER
         M, d = h_in.shape
         dev = h_in.device
+        pk = _pack_of(meta, dev)
         Lp = -(-Tp // 64) * 64
         hidden = torch.empty(n, M, d, device=dev, dtype=torch.float32)
         saved = []
@@ -169,10 +226,9 @@ class HubertLayersTrainFn(torch.autograd.Function):
             qw, qb, kw, kb, vw, vb, ow, ob, g1, b1n, w1, b1, w2, b2, g2, b2n = params[li * PER_LAYER:(li + 1) * PER_LAYER]
             wqkv, bqkv = _w16(torch.cat([qw, kw, vw], 0)), _f32(torch.cat([qb, kb, vb], 0))
             t1 = ops.layernorm(h, _f32(g1), _f32(b1n), eps)                                   # bf16
-            qkv = torch.empty(M + (Lp - Tp), 3 * d, device=dev, dtype=BF)
-            qkv[M:].zero_()
+            qkv = _qkv_rows(pk, M, Lp, Tp, d, dev)
             ops.gemm(t1, wqkv, bqkv, out=qkv[:M])
-            att = ops.attention(qkv[:M], B, Tp, H, valid_i32)
+            att = _attn_fwd(pk, qkv, M, B, Tp, H, valid_i32)
             xmid = ops.gemm(att, _w16(ow), _f32(ob), residual=h, out_f32=True)
             t2 = ops.layernorm(xmid, _f32(g2), _f32(b2n), eps)
             hm = ops.gemm(t2, _w16(w1), _f32(b1), ACT_GELU)
@@ -208,7 +264,7 @@ class HubertLayersTrainFn(torch.autograd.Function):
             ops.axpy_bf16(dxm, g, 1.0)                                 # + the residual path
             # xmid = h + out_proj(attn(qkv(t1))),  t1 = LN1(h)
             datt = ops.gemm(dxm, _w16(ow.t()))
-            dqkv = attention_bwd(qkv, att, datt, B, Tp, H, ctx.valid)
+            dqkv = _attn_bwd(_pack_of(m, datt.device), qkv, att, datt, B, Tp, H, ctx.valid)
             wqkv = torch.cat([qw, kw, vw], 0)
             dt1 = ops.gemm(dqkv, _w16(wqkv.t()))
             dh, dg1, db1n = ops.layernorm_bwd_bf16(h16, dt1, _f32(g1), eps, want)
@@ -264,7 +320,8 @@ class HubertLayersTrainFn(torch.autograd.Function):
             # y1 = dropout1(att Wo^T + bo) + h
             dy1 = dy1r if drop is None else ops.dropout_bf16(dy1r, drop["hidden"], s1)
             datt = ops.gemm(dy1, _w16(ow.t()))
-            dqkv = attention_bwd(qkv, att, datt, B, Tp, H, ctx.valid, None if drop is None or drop["attention"] <= 0 else (drop["attention"], sa))
+            dqkv = _attn_bwd(_pack_of(m, datt.device), qkv, att, datt, B, Tp, H, ctx.valid,
+                             None if drop is None or drop["attention"] <= 0 else (drop["attention"], sa))
             wqkv = torch.cat([qw, kw, vw], 0)
             dh = ops.gemm(dqkv, _w16(wqkv.t()), residual=dy1r)                 # [M, d] = dqkv Wqkv + dy1 (unmasked: the residual path)
             if want:
