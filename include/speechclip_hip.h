@@ -128,7 +128,11 @@ int sc_wave_layernorm(const float* wav, float* out, const int32_t* lens, int B, 
  * in ResidualAttentionBlock (clip_official.py:209; causal != 0 adds the text tower's build_attention_mask,
  * clip_official.py:249-262).  out: bf16 [B*T, H*64] rows of stride ld_out.
  * `flags`: SC_ATTN_CAUSAL (= 1, what a boolean `causal` used to pass) | SC_ATTN_F16: q / k / v / out are IEEE half instead of bf16 (the probabilities
- * are rounded to half too; scores, running maxima and sums stay fp32) -- the operand format of SC_GEMM_F16. */
+ * are rounded to half too; scores, running maxima and sums stay fp32) -- the operand format of SC_GEMM_F16.
+ * Rows past the key length (also sc_attention_fwd_dropout / sc_attention_fwd_packed): K / V rows t in [klens[b], T) that share the last 64-key tile with a valid key are
+ * loaded; their scores are replaced by -inf whatever K holds, but their V rows enter the P.V MFMA with P = 0.  PRECONDITION: V is FINITE on those rows (0 x Inf / NaN would
+ * reach every query row of the utterance); any finite value, and anything at all in K or in later tiles, is ignored bit for bit.  klens[b] <= 0 gives exact zeros, klens[b] > T
+ * means T.  (sc_attention_hd_fwd zeroes such V rows on load and has no such precondition.) */
 #define SC_ATTN_CAUSAL 0x1
 #define SC_ATTN_F16 0x2
 int sc_attention_fwd(const void* q, const void* k, const void* v, void* out, const int32_t* klens, int B, int H,

@@ -128,15 +128,27 @@ def _keep(seed, idx, p):
     return torch.from_numpy((h >= np.uint64(int(p * 4294967296.0))).astype(np.float32))
 
 
-def _keep_attn(seed, B, H, T, p):
-    """The attention-probability mask (csrc/common.h hash_pair): one hash per pair of adjacent keys of a query row, 16 bits each;
-    pair index = ((b*H + h)*T + query) * ceil(T/2) + (key >> 1); keep iff the half's 16 bits >= p * 2^16."""
-    rows = np.arange(B * H * T, dtype=np.uint64)[:, None]
-    keys = np.arange(T, dtype=np.uint64)[None, :]
-    pair = (rows * np.uint64((T + 1) // 2) + (keys >> np.uint64(1))) & np.uint64(0xffffffff)
+def _keep_rows(seed, row_ids, n_keys, stride, p):
+    """csrc/common.h hash_pair, restated for mask rows `row_ids`: one hash per pair of adjacent keys of a row, 16 bits each (even key: low half);
+    pair index = row_id * stride + (key >> 1); keep iff the half's 16 bits >= p * 2^16.  -> float [len(row_ids), n_keys], 1 = kept."""
+    rows = np.asarray(row_ids, dtype=np.uint64).reshape(-1, 1)
+    keys = np.arange(n_keys, dtype=np.uint64)[None, :]
+    pair = (rows * np.uint64(stride) + (keys >> np.uint64(1))) & np.uint64(0xffffffff)
     h = _hash32(((pair * np.uint64(0x9E3779B1)) + np.uint64(seed & 0xffffffff)) & np.uint64(0xffffffff))
     bits = np.where((keys & np.uint64(1)) == 1, h >> np.uint64(16), h & np.uint64(0xffff))
-    return torch.from_numpy((bits >= np.uint64(int(p * 65536.0))).astype(np.float32)).view(B, H, T, T)
+    return torch.from_numpy((bits >= np.uint64(int(p * 65536.0))).astype(np.float32))
+
+
+def _keep_attn(seed, B, H, T, p):
+    """The attention-probability mask of the uniform layout: row_id = (b*H + h)*T + query, pair stride ceil(T/2).  -> [B, H, T, T]"""
+    return _keep_rows(seed, np.arange(B * H * T), T, (T + 1) // 2, p).view(B, H, T, T)
+
+
+def _keep_attn_packed(seed, row_off_b, H, rows_b, Tmax, p):
+    """The mask of ONE utterance of a packed batch (sc_attention_fwd_packed, csrc/attention.hip drop_row / drop_pairs): row_id = (row_off[b] + query)*H + h,
+    pair stride ceil(Tmax/2) whatever the utterance's own row count.  -> [H, rows_b, rows_b]"""
+    ids = (row_off_b + np.arange(rows_b))[None, :] * H + np.arange(H)[:, None]
+    return _keep_rows(seed, ids.reshape(-1), rows_b, (Tmax + 1) // 2, p).view(H, rows_b, rows_b)
 
 
 def test_trained_layer_with_dropout_matches_autograd_with_the_same_masks():
