@@ -415,13 +415,35 @@ int sc_cls_pool_dz(const float* pp, const float* ds, const float* dzbar, const f
  *   sc_attention_fwd_packed  fairseq MHA with key-padding mask over packed q|k|v rows (drop_p > 0: the train-mode form)
  *   sc_unpack_rows           packed -> the reference's padded [n_layers][B][T_out][row] layout: out[l][b][t] = t < rows_b - halo ? src row : 0.
  *                            The encoder passes halo = 1: the last row of every utterance is the receptive-field halo (inexact, reads the
- *                            neighbouring utterance's samples) and is not exposed; frames >= max(valid_b, feat_len_b) are zeros. */
+ *                            neighbouring utterance's samples) and is not exposed; frames >= max(valid_b, feat_len_b) are zeros.
+ * Whole-encoder training on packed rows (speechclip_amd/train_front.py) adds the backward's per-utterance kernels; none of them uses atomics:
+ *   sc_conv0_bwd_packed / sc_conv0_wgrad_packed   sc_conv0_bwd / sc_conv0_wgrad with dy / du read at rows row_scale * row_off[b] + t and taken as zero for
+ *                            t >= row_scale * rows_b.  The wave stays the padded [B, ld]; the GroupNorm statistics and every sum of its backward run over all
+ *                            T0 frames of the padded length (frames the layout does not materialise carry no dy but still enter the mean-subtraction terms).
+ *   sc_posconv_finish_train_packed / sc_posconv_dgrad_finish_packed / sc_reverse_rows_packed_bf16   the packed forms of the three elementwise kernels over
+ *                            sc_posconv_conv_packed's slab layout; the time reversal runs inside each utterance's own rows.  dx = mask(ds + conv^T du) with
+ *                            convT = sc_posconv_conv_packed(reversed du, valid = rows_b, swapped weights); every row of u / s / dx / out is written.
+ *   sc_posconv_pack_gapped   out bf16 [G][slab_rows][D/G]: row lead + row_off[b] + b * gap + t of group g = row row_off[b] + t of x for t < min(lim[b], rows_b),
+ *                            zeros everywhere else (slab_rows >= lead + total_rows + B * gap; every row written).  With gap = Kw a window of Kw rows never sees
+ *                            two utterances, so the positional conv's dW is ONE [rows, cols] product: (x, lim = valid, lead = Kw/2) is its sliding-window
+ *                            operand and (du, lim = rows_b, G = 1, lead = 0) the gradient in the same row numbering. */
 int sc_conv0_fwd_packed(const float* wav, int64_t ld, int64_t L, const float* w, const float* bias, const float* coef, void* out, int B,
                         int C, int T0, const int32_t* row_off, int row_scale, int Pmax, int mode, void* wfrag_ws, void* stream);
 int sc_posconv_conv_packed(const void* x, const int32_t* valid, const int32_t* row_off, const void* wg, void* conv, int B, int Tmax, int D, int G,
                            int Kw, void* stream);
 int sc_posconv_finish_packed(const void* x, const int32_t* valid, const int32_t* row_off, const void* conv, const float* bias, const float* gamma,
                              const float* beta, void* out, int B, int64_t total_rows, int D, int G, int out_f32, float eps, void* stream);
+int sc_conv0_bwd_packed(const float* wav, int64_t ld, const float* w, const float* gamma, const float* beta, const void* dy, float* part, int B, int C,
+                        int T0, const int32_t* row_off, int row_scale, float eps, void* stream);
+int sc_conv0_wgrad_packed(const float* wav, int64_t ld, const void* du, float* part, int B, int C, int T0, const int32_t* row_off, int row_scale,
+                          void* stream);
+int sc_posconv_finish_train_packed(const void* x, const int32_t* valid, const int32_t* row_off, const void* conv, const float* bias, void* u, void* s,
+                                   int B, int64_t total_rows, int D, int G, void* stream);
+int sc_posconv_dgrad_finish_packed(const void* convT, const void* ds, const int32_t* valid, const int32_t* row_off, void* dx, int B, int64_t total_rows,
+                                   int D, int G, void* stream);
+int sc_reverse_rows_packed_bf16(const void* in, const int32_t* row_off, void* out, int B, int64_t total_rows, int D, void* stream);
+int sc_posconv_pack_gapped(const void* x, const int32_t* lim, const int32_t* row_off, void* out, int B, int64_t total_rows, int D, int G, int gap,
+                           int lead, int64_t slab_rows, void* stream);
 int sc_attention_fwd_packed(const void* q, const void* k, const void* v, void* out, const int32_t* klens, const int32_t* row_off, int B, int H,
                             int Tmax, int64_t total_rows, int head_dim, int64_t ld_qkv, int64_t ld_out, float scale, float drop_p, uint32_t seed,
                             int flags /* SC_ATTN_F16 or 0 */, void* stream);

@@ -101,6 +101,12 @@ def _declare(L):
         "sc_conv0_fwd_packed": ([P, L64, L64, P, P, P, P, I, I, I, P, I, I, I, P, P], c_int),
         "sc_posconv_conv_packed": ([P, P, P, P, P, I, I, I, I, I, P], c_int),
         "sc_posconv_finish_packed": ([P, P, P, P, P, P, P, P, I, L64, I, I, I, F, P], c_int),
+        "sc_conv0_bwd_packed": ([P, L64, P, P, P, P, P, I, I, I, P, I, F, P], c_int),
+        "sc_conv0_wgrad_packed": ([P, L64, P, P, I, I, I, P, I, P], c_int),
+        "sc_posconv_finish_train_packed": ([P, P, P, P, P, P, P, I, L64, I, I, P], c_int),
+        "sc_posconv_dgrad_finish_packed": ([P, P, P, P, P, I, L64, I, I, P], c_int),
+        "sc_reverse_rows_packed_bf16": ([P, P, P, I, L64, I, P], c_int),
+        "sc_posconv_pack_gapped": ([P, P, P, P, I, L64, I, I, I, I, L64, P], c_int),
         "sc_attention_fwd_packed": ([P, P, P, P, P, P, I, I, I, L64, I, L64, L64, F, F, U32, I, P], c_int),
         "sc_unpack_rows": ([P, L64, P, P, L64, I, I, I, I, I, P], c_int),
         "sc_pack_rows": ([P, L64, P, P, L64, I, I, I, L64, I, I, P], c_int),

@@ -9,6 +9,13 @@
 //   sc_reverse_rows_bf16      out[b, t, :] = in[b, T-1-t, :]
 //   sc_conv0_bwd              conv layer 0 (Conv1d(1 -> C, k=10, s=5, no bias) -> GroupNorm(C groups) over time -> GELU) backward from the wave:
 //                             per-(b, c) partial gradients of the conv weight [10], gamma and beta (summed over b by sc_colsum)
+// Packed (padding-free) batches -- utterance b owns rows [row_off[b], row_off[b + 1]) at transformer level and row_scale times that range at conv
+// layer 0 (module/hubert.py: packed_geometry) -- have their own forms of the per-utterance kernels; every GEMM-shaped part is row-wise and runs as it is:
+//   sc_conv0_bwd_packed / sc_conv0_wgrad_packed   dy / du read at rows row_scale * row_off[b] + t, zero for frames the layout does not materialise
+//                             (the GroupNorm sums still run over all T0 frames of the padded length)
+//   sc_posconv_finish_train_packed / sc_posconv_dgrad_finish_packed / sc_reverse_rows_packed_bf16   the elementwise kernels over sc_posconv_conv_packed's
+//                             slab layout ([G][rows_b][cg] at element row_off[b] * D), time reversed inside each utterance's own rows
+//   sc_posconv_pack_gapped    the window slab of the weight gradient with Kw zero rows between utterances, so that dW stays ONE [rows, cols] product
 #include "common.h"
 #include "../../include/speechclip_hip.h"
 
@@ -77,10 +84,13 @@ __global__ __launch_bounds__(256) void reverse_rows_kernel(const bf16_t* __restr
 // recomputed from the wave each time (10 FMAs): (A) mean / variance of u over time, (B) S1 = sum dzhat, S2 = sum dzhat uhat, dgamma, dbeta,
 // (C) du = rstd (dzhat - S1/T - uhat S2/T) and dw[j] += du wav[5 t + j].  dy rows >= T0 of an utterance do not exist in the reference (alignment
 // padding of the channels-last buffer) and are not read.
+// PACKED: utterance b's dy rows start at row_scale * row_off[b] and only row_scale * rows_b of them exist; later frames carry no gradient (dz = 0) but still
+// take part in the two mean-subtraction terms of sweep (C): a frame the layout does not materialise can still see non-zero samples near the utterance's end.
 constexpr int C0_K = 10, C0_S = 5;
+template <bool PACKED>
 __global__ __launch_bounds__(256) void conv0_bwd_kernel(const float* __restrict__ wav, int64_t ld, const float* __restrict__ w, const float* __restrict__ gamma,
                                                         const float* __restrict__ beta, const bf16_t* __restrict__ dy, float* __restrict__ part, int C, int T0,
-                                                        int P, float eps) {
+                                                        int P, float eps, const int32_t* __restrict__ row_off, int row_scale) {
     __shared__ float red[4][64][12];
     const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);   // scalar: the frame index below is wave-uniform,
     const int b = blockIdx.y, c = blockIdx.x * 64 + lane;                                            // so the ten wave samples of a frame are scalar loads
@@ -117,10 +127,11 @@ __global__ __launch_bounds__(256) void conv0_bwd_kernel(const float* __restrict_
     const float mean = (float)mean_d;
     const float rstd = rsqrtf((float)(sq / (double)T0 - mean_d * mean_d) + eps);
     const float gm = gamma[c], bt = beta[c];
-    const bf16_t* dyb = dy + (int64_t)b * P * C + c;
+    const bf16_t* dyb = dy + (PACKED ? (int64_t)row_scale * row_off[b] : (int64_t)b * P) * C + c;
+    const int tlim = PACKED ? min(T0, row_scale * (row_off[b + 1] - row_off[b])) : T0;      // frames with a gradient
     // (B)
     float s1 = 0.f, s2 = 0.f, dg = 0.f, db = 0.f;
-    for (int t = wave; t < T0; t += 4) {
+    for (int t = wave; t < tlim; t += 4) {
         const float uh = (conv_at(t, x) - mean) * rstd;
         const float dz = bf2f(dyb[(int64_t)t * C]) * gelu_grad(fmaf(gm, uh, bt));
         dg = fmaf(dz, uh, dg);
@@ -139,7 +150,7 @@ __global__ __launch_bounds__(256) void conv0_bwd_kernel(const float* __restrict_
     for (int j = 0; j < C0_K; ++j) dw[j] = 0.f;
     for (int t = wave; t < T0; t += 4) {
         const float uh = (conv_at(t, x) - mean) * rstd;
-        const float dz = bf2f(dyb[(int64_t)t * C]) * gelu_grad(fmaf(gm, uh, bt));
+        const float dz = (!PACKED || t < tlim) ? bf2f(dyb[(int64_t)t * C]) * gelu_grad(fmaf(gm, uh, bt)) : 0.f;
         const float du = rstd * (dz * gm - m1 - uh * m2);
 #pragma unroll
         for (int j = 0; j < C0_K; ++j) dw[j] = fmaf(du, x[j], dw[j]);
@@ -158,17 +169,19 @@ __global__ __launch_bounds__(256) void conv0_bwd_kernel(const float* __restrict_
 
 // conv layer 0 of the LayerNorm extractor (HuBERT-large: Conv1d(1 -> C, k 10, s 5, bias) -> LayerNorm(C) -> GELU): the LayerNorm / GELU part of the
 // backward runs on the row kernels, which leaves dw[c, j] = sum_t du[t, c] wav[5 t + j] and dbias[c] = sum_t du[t, c] per utterance.
+template <bool PACKED>      // du rows of utterance b at row_scale * row_off[b] .., zero beyond the row_scale * rows_b the layout holds
 __global__ __launch_bounds__(256) void conv0_wgrad_kernel(const float* __restrict__ wav, int64_t ld, const bf16_t* __restrict__ du, float* __restrict__ part,
-                                                          int C, int T0, int P) {
+                                                          int C, int T0, int P, const int32_t* __restrict__ row_off, int row_scale) {
     __shared__ float red[4][64][12];
     const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int b = blockIdx.y, c = blockIdx.x * 64 + lane;
     const float* wv = wav + (int64_t)b * ld;
-    const bf16_t* dub = du + (int64_t)b * P * C + c;
+    const bf16_t* dub = du + (PACKED ? (int64_t)row_scale * row_off[b] : (int64_t)b * P) * C + c;
+    const int tlim = PACKED ? min(T0, row_scale * (row_off[b + 1] - row_off[b])) : T0;
     float acc[12];
 #pragma unroll
     for (int j = 0; j < 12; ++j) acc[j] = 0.f;
-    for (int t = wave; t < T0; t += 4) {
+    for (int t = wave; t < tlim; t += 4) {
         const float g = bf2f(dub[(int64_t)t * C]);
 #pragma unroll
         for (int j = 0; j < C0_K; ++j) acc[j] = fmaf(g, wv[t * C0_S + j], acc[j]);
@@ -183,6 +196,104 @@ __global__ __launch_bounds__(256) void conv0_wgrad_kernel(const float* __restric
     }
 }
 
+// ------------------------------------------------------------------------------------------------ packed (padding-free) batches
+// Row-streaming kernels over packed rows: a thread owns 8 adjacent channels (one 16-byte load / store per tensor; cg % 8 == 0 keeps them in one group).
+// The owning utterance of a row is found by binary search in row_off (row_off[b] <= row < row_off[b + 1]), as posconv_finish_kernel does.
+__device__ __forceinline__ int pk_find(const int32_t* __restrict__ off, int B, int64_t row) {
+    int lo = 0, hi = B;
+    while (hi - lo > 1) { const int mid = (lo + hi) >> 1; if ((int64_t)off[mid] <= row) lo = mid; else hi = mid; }
+    return lo;
+}
+__device__ __forceinline__ void pk_unpack8(const uint4 v, float (&f)[8]) {
+    f[0] = lo2f(v.x); f[1] = hi2f(v.x); f[2] = lo2f(v.y); f[3] = hi2f(v.y); f[4] = lo2f(v.z); f[5] = hi2f(v.z); f[6] = lo2f(v.w); f[7] = hi2f(v.w);
+}
+__device__ __forceinline__ uint4 pk_pack8(const float (&f)[8]) {
+    return make_uint4(pack2bf(f[0], f[1]), pack2bf(f[2], f[3]), pack2bf(f[4], f[5]), pack2bf(f[6], f[7]));
+}
+
+// posconv_finish_train_kernel over packed rows: conv slab of utterance b = [G][rows_b][cg] at element row_off[b] * D
+__global__ __launch_bounds__(256) void posconv_finish_train_packed_kernel(const bf16_t* __restrict__ x, const int32_t* __restrict__ valid,
+                                                                          const int32_t* __restrict__ row_off, const bf16_t* __restrict__ conv,
+                                                                          const float* __restrict__ bias, bf16_t* __restrict__ u, bf16_t* __restrict__ s, int B,
+                                                                          int64_t total_rows, int D, int G) {
+    const int64_t idx = ((int64_t)blockIdx.x * 256 + threadIdx.x) * 8;
+    if (idx >= total_rows * D) return;
+    const int64_t row = idx / D;
+    const int e = (int)(idx - row * D);
+    const int b = pk_find(row_off, B, row);
+    const int r0 = row_off[b], t = (int)(row - r0), rows_b = row_off[b + 1] - r0;
+    const int cg = D / G, g = e / cg, ci = e - g * cg;
+    float cv[8], xv[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f}, uv[8], sv[8];
+    pk_unpack8(*(const uint4*)(conv + ((int64_t)r0 * G + (int64_t)g * rows_b + t) * cg + ci), cv);
+    if (t < valid[b]) pk_unpack8(*(const uint4*)(x + idx), xv);
+    const f32x4_t b0 = *(const f32x4_t*)(bias + e), b1 = *(const f32x4_t*)(bias + e + 4);
+#pragma unroll
+    for (int i = 0; i < 8; ++i) uv[i] = cv[i] + (i < 4 ? b0[i] : b1[i - 4]);
+    const uint4 uo = pk_pack8(uv);
+    float ur[8];
+    pk_unpack8(uo, ur);               // gelu of the bf16-ROUNDED pre-activation, as the padded kernel
+#pragma unroll
+    for (int i = 0; i < 8; ++i) sv[i] = xv[i] + gelu_erf_precise(ur[i]);
+    *(uint4*)(u + idx) = uo;
+    *(uint4*)(s + idx) = pk_pack8(sv);
+}
+
+// dx[row, e] = t < valid[b] ? ds[row, e] + convT[b][g][rows_b - 1 - t][ci] : 0 (convT: sc_posconv_conv_packed of the per-utterance reversed du)
+__global__ __launch_bounds__(256) void posconv_dgrad_finish_packed_kernel(const bf16_t* __restrict__ convT, const bf16_t* __restrict__ ds,
+                                                                          const int32_t* __restrict__ valid, const int32_t* __restrict__ row_off,
+                                                                          bf16_t* __restrict__ dx, int B, int64_t total_rows, int D, int G) {
+    const int64_t idx = ((int64_t)blockIdx.x * 256 + threadIdx.x) * 8;
+    if (idx >= total_rows * D) return;
+    const int64_t row = idx / D;
+    const int e = (int)(idx - row * D);
+    const int b = pk_find(row_off, B, row);
+    const int r0 = row_off[b], t = (int)(row - r0), rows_b = row_off[b + 1] - r0;
+    uint4 o = make_uint4(0u, 0u, 0u, 0u);
+    if (t < valid[b]) {
+        const int cg = D / G, g = e / cg, ci = e - g * cg;
+        float cv[8], dv[8], ov[8];
+        pk_unpack8(*(const uint4*)(convT + ((int64_t)r0 * G + (int64_t)g * rows_b + (rows_b - 1 - t)) * cg + ci), cv);
+        pk_unpack8(*(const uint4*)(ds + idx), dv);
+#pragma unroll
+        for (int i = 0; i < 8; ++i) ov[i] = cv[i] + dv[i];
+        o = pk_pack8(ov);
+    }
+    *(uint4*)(dx + idx) = o;
+}
+
+// out[row_off[b] + rows_b - 1 - t, :] = in[row_off[b] + t, :]
+__global__ __launch_bounds__(256) void reverse_rows_packed_kernel(const bf16_t* __restrict__ in, const int32_t* __restrict__ row_off, bf16_t* __restrict__ out,
+                                                                  int B, int64_t total_rows, int D) {
+    const int64_t idx = ((int64_t)blockIdx.x * 256 + threadIdx.x) * 8;
+    if (idx >= total_rows * D) return;
+    const int64_t row = idx / D;
+    const int e = (int)(idx - row * D);
+    const int b = pk_find(row_off, B, row);
+    const int r0 = row_off[b], t = (int)(row - r0), rows_b = row_off[b + 1] - r0;
+    *(uint4*)(out + ((int64_t)r0 + (rows_b - 1 - t)) * D + e) = *(const uint4*)(in + idx);
+}
+
+// out[g][lead + row_off[b] + b * gap + t][c] = t < min(lim[b], rows_b) ? x[row_off[b] + t][g * cg + c] : 0; every other row of the [G][slab_rows][cg] slab is zero.
+// Utterance b starts at gapped row row_off[b] + b * gap: with gap = Kw zero rows between neighbours a window of Kw rows never sees two utterances.
+__global__ __launch_bounds__(256) void posconv_pack_gapped_kernel(const bf16_t* __restrict__ x, const int32_t* __restrict__ lim, const int32_t* __restrict__ row_off,
+                                                                  bf16_t* __restrict__ out, int B, int D, int G, int gap, int lead, int64_t slab_rows) {
+    const int64_t idx = ((int64_t)blockIdx.x * 256 + threadIdx.x) * 8;
+    if (idx >= slab_rows * D) return;
+    const int64_t r = idx / D;
+    const int e = (int)(idx - r * D);
+    const int cg = D / G, g = e / cg, ci = e - g * cg;
+    const int64_t p = r - lead;
+    uint4 v = make_uint4(0u, 0u, 0u, 0u);
+    if (p >= 0) {
+        int lo = 0, hi = B;          // the last utterance whose gapped start is <= p
+        while (hi - lo > 1) { const int mid = (lo + hi) >> 1; if ((int64_t)row_off[mid] + (int64_t)mid * gap <= p) lo = mid; else hi = mid; }
+        const int r0 = row_off[lo], rows_b = row_off[lo + 1] - r0;
+        const int64_t t = p - r0 - (int64_t)lo * gap;
+        if (t < rows_b && t < lim[lo]) v = *(const uint4*)(x + ((int64_t)r0 + t) * D + e);
+    }
+    *(uint4*)(out + ((int64_t)g * slab_rows + r) * cg + ci) = v;
+}
+
 }  // namespace
 
 extern "C" int sc_conv0_wgrad(const float* wav, int64_t ld, const void* du, float* part, int B, int C, int T0, int P, void* stream) {
@@ -190,7 +301,7 @@ extern "C" int sc_conv0_wgrad(const float* wav, int64_t ld, const void* du, floa
     SC_CHECK_ARG(C % 64 == 0 && B <= 65535, "sc_conv0_wgrad: C must be a multiple of 64, B <= 65535");
     SC_CHECK_ARG(T0 >= 1 && P >= T0 && ld >= (int64_t)(T0 - 1) * C0_S + C0_K, "sc_conv0_wgrad: T0=%d P=%d ld=%lld inconsistent", T0, P, (long long)ld);
     if (B <= 0) return 0;
-    hipLaunchKernelGGL(conv0_wgrad_kernel, dim3(C / 64, B), dim3(256), 0, (hipStream_t)stream, wav, ld, (const bf16_t*)du, part, C, T0, P);
+    hipLaunchKernelGGL(conv0_wgrad_kernel<false>, dim3(C / 64, B), dim3(256), 0, (hipStream_t)stream, wav, ld, (const bf16_t*)du, part, C, T0, P, nullptr, 0);
     SC_CHECK_LAUNCH();
     return 0;
 }
@@ -234,7 +345,90 @@ extern "C" int sc_conv0_bwd(const float* wav, int64_t ld, const float* w, const 
     SC_CHECK_ARG(C % 64 == 0 && B <= 65535, "sc_conv0_bwd: C must be a multiple of 64, B <= 65535");
     SC_CHECK_ARG(T0 >= 1 && P >= T0 && ld >= (int64_t)(T0 - 1) * C0_S + C0_K, "sc_conv0_bwd: T0=%d P=%d ld=%lld inconsistent", T0, P, (long long)ld);
     if (B <= 0) return 0;
-    hipLaunchKernelGGL(conv0_bwd_kernel, dim3(C / 64, B), dim3(256), 0, (hipStream_t)stream, wav, ld, w, gamma, beta, (const bf16_t*)dy, part, C, T0, P, eps);
+    hipLaunchKernelGGL(conv0_bwd_kernel<false>, dim3(C / 64, B), dim3(256), 0, (hipStream_t)stream, wav, ld, w, gamma, beta, (const bf16_t*)dy, part, C, T0, P, eps,
+                       nullptr, 0);
+    SC_CHECK_LAUNCH();
+    return 0;
+}
+
+// ------------------------------------------------------------------------------------------------ packed (padding-free) batches
+// row_off: B + 1 device ints in transformer rows (row_off[B] = total_rows); the callers' buffers hold row_scale * total_rows rows at conv layer 0.
+extern "C" int sc_conv0_bwd_packed(const float* wav, int64_t ld, const float* w, const float* gamma, const float* beta, const void* dy, float* part, int B, int C,
+                                   int T0, const int32_t* row_off, int row_scale, float eps, void* stream) {
+    SC_CHECK_ARG(wav && w && gamma && beta && dy && part && row_off, "sc_conv0_bwd_packed: null operand");
+    SC_CHECK_ARG(C % 64 == 0 && B <= 65535, "sc_conv0_bwd_packed: C must be a multiple of 64, B <= 65535");
+    SC_CHECK_ARG(T0 >= 1 && row_scale >= 1 && ld >= (int64_t)(T0 - 1) * C0_S + C0_K, "sc_conv0_bwd_packed: T0=%d row_scale=%d ld=%lld inconsistent", T0, row_scale,
+                 (long long)ld);
+    if (B <= 0) return 0;
+    hipLaunchKernelGGL(conv0_bwd_kernel<true>, dim3(C / 64, B), dim3(256), 0, (hipStream_t)stream, wav, ld, w, gamma, beta, (const bf16_t*)dy, part, C, T0, 0, eps,
+                       row_off, row_scale);
+    SC_CHECK_LAUNCH();
+    return 0;
+}
+
+extern "C" int sc_conv0_wgrad_packed(const float* wav, int64_t ld, const void* du, float* part, int B, int C, int T0, const int32_t* row_off, int row_scale,
+                                     void* stream) {
+    SC_CHECK_ARG(wav && du && part && row_off, "sc_conv0_wgrad_packed: null operand");
+    SC_CHECK_ARG(C % 64 == 0 && B <= 65535, "sc_conv0_wgrad_packed: C must be a multiple of 64, B <= 65535");
+    SC_CHECK_ARG(T0 >= 1 && row_scale >= 1 && ld >= (int64_t)(T0 - 1) * C0_S + C0_K, "sc_conv0_wgrad_packed: T0=%d row_scale=%d ld=%lld inconsistent", T0, row_scale,
+                 (long long)ld);
+    if (B <= 0) return 0;
+    hipLaunchKernelGGL(conv0_wgrad_kernel<true>, dim3(C / 64, B), dim3(256), 0, (hipStream_t)stream, wav, ld, (const bf16_t*)du, part, C, T0, 0, row_off, row_scale);
+    SC_CHECK_LAUNCH();
+    return 0;
+}
+
+#define SC_PACKED_ROWS_CHECK(name)                                                                                                             \
+    SC_CHECK_ARG(B > 0 && total_rows > 0 && total_rows * D < (int64_t)0x7fffffff * 8, name ": B=%d total_rows=%lld out of range", B, (long long)total_rows)
+
+extern "C" int sc_posconv_finish_train_packed(const void* x, const int32_t* valid, const int32_t* row_off, const void* conv, const float* bias, void* u, void* s,
+                                              int B, int64_t total_rows, int D, int G, void* stream) {
+    SC_CHECK_ARG(x && valid && row_off && conv && bias && u && s, "sc_posconv_finish_train_packed: null operand");
+    SC_CHECK_ARG(G > 0 && D % G == 0 && (D / G) % 8 == 0, "sc_posconv_finish_train_packed: D/G must be a multiple of 8");
+    SC_PACKED_ROWS_CHECK("sc_posconv_finish_train_packed");
+    const int64_t n8 = total_rows * D / 8;
+    hipLaunchKernelGGL(posconv_finish_train_packed_kernel, dim3((unsigned)((n8 + 255) / 256)), dim3(256), 0, (hipStream_t)stream, (const bf16_t*)x, valid, row_off,
+                       (const bf16_t*)conv, bias, (bf16_t*)u, (bf16_t*)s, B, total_rows, D, G);
+    SC_CHECK_LAUNCH();
+    return 0;
+}
+
+extern "C" int sc_posconv_dgrad_finish_packed(const void* convT, const void* ds, const int32_t* valid, const int32_t* row_off, void* dx, int B, int64_t total_rows,
+                                              int D, int G, void* stream) {
+    SC_CHECK_ARG(convT && ds && valid && row_off && dx, "sc_posconv_dgrad_finish_packed: null operand");
+    SC_CHECK_ARG(G > 0 && D % G == 0 && (D / G) % 8 == 0, "sc_posconv_dgrad_finish_packed: D/G must be a multiple of 8");
+    SC_PACKED_ROWS_CHECK("sc_posconv_dgrad_finish_packed");
+    const int64_t n8 = total_rows * D / 8;
+    hipLaunchKernelGGL(posconv_dgrad_finish_packed_kernel, dim3((unsigned)((n8 + 255) / 256)), dim3(256), 0, (hipStream_t)stream, (const bf16_t*)convT,
+                       (const bf16_t*)ds, valid, row_off, (bf16_t*)dx, B, total_rows, D, G);
+    SC_CHECK_LAUNCH();
+    return 0;
+}
+
+extern "C" int sc_reverse_rows_packed_bf16(const void* in, const int32_t* row_off, void* out, int B, int64_t total_rows, int D, void* stream) {
+    SC_CHECK_ARG(in && out && row_off && in != out, "sc_reverse_rows_packed_bf16: null operand or in-place");
+    SC_CHECK_ARG(D % 8 == 0, "sc_reverse_rows_packed_bf16: D must be a multiple of 8");
+    SC_PACKED_ROWS_CHECK("sc_reverse_rows_packed_bf16");
+    const int64_t n8 = total_rows * D / 8;
+    hipLaunchKernelGGL(reverse_rows_packed_kernel, dim3((unsigned)((n8 + 255) / 256)), dim3(256), 0, (hipStream_t)stream, (const bf16_t*)in, row_off, (bf16_t*)out,
+                       B, total_rows, D);
+    SC_CHECK_LAUNCH();
+    return 0;
+}
+
+// out bf16 [G][slab_rows][D/G]: row lead + row_off[b] + b * gap + t of group g = row row_off[b] + t of x (columns of group g) for t < min(lim[b], rows_b), zeros
+// everywhere else; every row of the slab is written.  slab_rows >= lead + row_off[B] + B * gap.  The weight gradient of the positional conv uses it twice:
+// (x, lim = valid, G groups, lead = Kw / 2) is the sliding-window operand, (du, lim = rows, G = 1, lead = 0) the gradient in the same row numbering.
+extern "C" int sc_posconv_pack_gapped(const void* x, const int32_t* lim, const int32_t* row_off, void* out, int B, int64_t total_rows, int D, int G, int gap,
+                                      int lead, int64_t slab_rows, void* stream) {
+    SC_CHECK_ARG(x && lim && row_off && out, "sc_posconv_pack_gapped: null operand");
+    SC_CHECK_ARG(G > 0 && D % G == 0 && (D / G) % 8 == 0, "sc_posconv_pack_gapped: D/G must be a multiple of 8");
+    SC_CHECK_ARG(gap >= 0 && lead >= 0 && slab_rows >= lead + total_rows + (int64_t)B * gap, "sc_posconv_pack_gapped: slab_rows=%lld too small", (long long)slab_rows);
+    SC_PACKED_ROWS_CHECK("sc_posconv_pack_gapped");
+    SC_CHECK_ARG(slab_rows * D < (int64_t)0x7fffffff * 8, "sc_posconv_pack_gapped: slab too large");
+    const int64_t n8 = slab_rows * D / 8;
+    hipLaunchKernelGGL(posconv_pack_gapped_kernel, dim3((unsigned)((n8 + 255) / 256)), dim3(256), 0, (hipStream_t)stream, (const bf16_t*)x, lim, row_off,
+                       (bf16_t*)out, B, D, G, gap, lead, slab_rows);
     SC_CHECK_LAUNCH();
     return 0;
 }

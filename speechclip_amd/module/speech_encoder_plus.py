@@ -312,6 +312,14 @@ def _forward_finetune(self, padded, lens, feat_select_idx, return_hidden_states,
         valid = enc.valid_frames(lens, padded.shape[1], T)
         fmeta = dict(conv_layers=[tuple(c) for c in cfg.conv_layers], T0=T0, P0=P0, Tp=Tp, d=d, G=cfg.conv_pos_groups, Kw=cfg.conv_pos,
                      grad_mult=float(enc.feature_grad_mult), normalize=bool(cfg.normalize))
+        # Padding-free whole-encoder training: the `_pack_plan` decision of the frozen forward and layer fine-tuning under SC_VARLEN_PACK=1; when it
+        # packs, the front end, every layer and the layer mix run on sum_b rows_b rows and [B, T, d] is restored at the boundary only.
+        pack = self._pack_plan(padded, lens)
+        if pack is not None and os.environ.get("SC_VARLEN_PACK", "auto") != "1":
+            pack = None      # `auto` stays padded for this mode until packing is measured faster on it; SC_VARLEN_PACK=1 opts in
+        if pack is not None:
+            off = ops.dev_ints(pack["row_off"], torch.int32, dev)
+            fmeta["pack"] = dict(row_off=off, rows_max=pack["rows_max"], total=pack["total"], scale0=pack["scale0"])
         valid_dev = ops.dev_ints(valid, torch.int32, dev)
         if cfg.layer_norm_first:
             h_front = HubertFrontLNTrainFn.apply(fmeta, padded.contiguous(), ops.dev_ints(lens, torch.int32, dev), valid_dev, *front_params_ln(enc))
@@ -319,12 +327,13 @@ def _forward_finetune(self, padded, lens, feat_select_idx, return_hidden_states,
             if drop_seed is not None:
                 r = enc.dropout_rates()
                 fmeta["drop"] = dict(features=r["features"], hidden=r["hidden"], seed=int(drop_seed))
-            h_front = HubertFrontTrainFn.apply(fmeta, padded.contiguous(), valid_dev, *front_params(enc))      # [B*Tp, d]
+            h_front = HubertFrontTrainFn.apply(fmeta, padded.contiguous(), valid_dev, *front_params(enc))      # [B*Tp, d] ([total, d] when packed)
+        if pack is not None:
+            return self._forward_finetune_packed(padded, lens, return_hidden_states, drop_seed, pack, h_front=h_front)
         hidden = None
     else:
         # Padding-free fine-tuning: the frozen layers below L0, the trained layers and the layer mix all run on sum_b rows_b packed rows; the reference's
-        # [B, T, d] layout is restored at the boundary only.  Same SC_VARLEN_PACK=0|1|auto rule as the frozen forward (`_pack_plan`).  Whole-encoder training
-        # (train_front) stays padded.
+        # [B, T, d] layout is restored at the boundary only.  Same SC_VARLEN_PACK=0|1|auto rule as the frozen forward (`_pack_plan`).
         pack = self._pack_plan(padded, lens)
         if pack is not None:
             return self._forward_finetune_packed(padded, lens, return_hidden_states, drop_seed, pack)
@@ -357,17 +366,21 @@ def _forward_finetune(self, padded, lens, feat_select_idx, return_hidden_states,
 FairseqSpeechEncoder_Hubert._forward_finetune = _forward_finetune
 
 
-def _forward_finetune_packed(self, padded, lens, return_hidden_states, drop_seed, pack):
+def _forward_finetune_packed(self, padded, lens, return_hidden_states, drop_seed, pack, h_front=None):
     """_forward_finetune over packed rows (pack = packed_geometry): utterance b owns rows pack["row_off"][b] .. of every tensor.  The attention of the trained
     layers runs on sc_attention_fwd_packed / sc_attention_bwd_packed; the mixed frames go back to [B, T, d] through a differentiable unpack (forward
-    sc_unpack_rows with halo = 1, backward sc_pack_rows), so the heads see what the frozen packed path hands them."""
+    sc_unpack_rows with halo = 1, backward sc_pack_rows), so the heads see what the frozen packed path hands them.  h_front (whole-encoder training): hidden
+    state 0 [total, d] from the packed front-end node, attached to the graph; every layer trains on top of it."""
     from ..train_hubert import HubertLayersTrainFn, UnpackRowsFn, WeightedSumTrainFn, layer_params
     enc = self.encoder
     cfg = enc.cfg
     dev = padded.device
     L0, nl = self.train_layers[0], cfg.encoder_layers
     B, d = padded.shape[0], cfg.encoder_embed_dim
-    hidden, T, _, valid = enc.extract_all_layers(padded, lens, stop_layer=L0, dropout_seed=drop_seed, pack=pack)      # [L0 + 1, total, d]
+    if h_front is None:
+        hidden, T, _, valid = enc.extract_all_layers(padded, lens, stop_layer=L0, dropout_seed=drop_seed, pack=pack)      # [L0 + 1, total, d]
+    else:
+        T, valid = pack["T"], pack["valid"]
     M = pack["total"]
     off = ops.dev_ints(pack["row_off"], torch.int32, dev)
     params = []
@@ -378,9 +391,10 @@ def _forward_finetune_packed(self, padded, lens, return_hidden_states, drop_seed
     if drop_seed is not None:
         r = enc.dropout_rates()
         meta["drop"] = dict(hidden=r["hidden"], attention=r["attention"], activation=r["activation"], seed=(int(drop_seed) * 2654435761 + 97) & 0x7fffffff)
-    h_in = hidden[L0].clone()                       # the engine's hidden buffer is a reused workspace
+    h_in = hidden[L0].clone() if h_front is None else h_front      # the engine's hidden buffer is a reused workspace
     hi = HubertLayersTrainFn.apply(meta, h_in, ops.dev_ints(valid, torch.int32, dev), *params)      # [nl - L0, total, d]
-    hidden_all = torch.cat([hidden[:L0 + 1].detach(), hi], 0)                                        # [nl + 1, total, d]
+    below = hidden[:L0 + 1].detach() if h_front is None else h_front.view(1, M, d)
+    hidden_all = torch.cat([below, hi], 0)                                                           # [nl + 1, total, d]
     ws = self.weightedsum_layer
     mixed = UnpackRowsFn.apply(WeightedSumTrainFn.apply(hidden_all, ws.weights, ws.normalize_features), off, B, T, 1)          # [B, T, d]
     states = ops.unpack_rows(hidden_all.detach(), off, B, T, halo=1)                                 # [nl + 1, B, T, d], zeros beyond each utterance

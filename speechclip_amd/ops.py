@@ -428,6 +428,7 @@ def posconv(x, valid_i32, wg, bias, gamma, beta, B, Tp, D, G, Kw, out=None, out_
 
 # ---------------------------------------------------------------------------------------------- padding-free (packed) batches
 # Utterance b owns rows [row_off[b], row_off[b + 1]) of every transformer-level tensor (module/hubert.py: extract_all_layers_packed).
+# The forward entries follow; the backward's packed entries (whole-encoder training on packed rows, train_front.py) sit with the front-end backward below.
 def conv0_packed(wav, w, T0, row_off_i32, row_scale, rows_max, total_rows, gn_gamma=None, gn_beta=None, bias=None, eps=1e-5, out=None, ln_coef=None):
     """ops.conv0 writing utterance b at rows row_scale * row_off[b] ...; the GroupNorm statistics are those of the padded length T0."""
     _need_cuda(wav, w, row_off_i32)
@@ -1104,6 +1105,83 @@ def conv0_wgrad(wav, du, C, T0, P):
     check(lib().sc_conv0_wgrad(ptr(wav), L, ptr(du), ptr(part), B, C, T0, P, stream()), "sc_conv0_wgrad")
     tot = colsum(part).view(C, 12)
     return tot[:, :10].contiguous(), tot[:, 10].contiguous()
+
+
+# ---- the same on packed rows (padding-free whole-encoder training): utterance b owns rows [row_off[b], row_off[b + 1]) of every transformer-level tensor
+def posconv_conv_packed(x, lim_i32, row_off_i32, wg, B, rows_max, total_rows, D, G, Kw):
+    """posconv_conv over packed rows: x bf16 [total_rows, D] (rows t >= lim[b] of utterance b read as zero) -> conv slabs, utterance b = [G][rows_b][D/G] at
+    element row_off[b] * D."""
+    _need_cuda(x, wg, row_off_i32)
+    assert x.dtype == bf16 and x.is_contiguous() and x.shape == (total_rows, D)
+    conv = torch.empty(total_rows * D, device=x.device, dtype=bf16)
+    rc = lib().sc_posconv_conv_packed(ptr(x), ptr(lim_i32), ptr(row_off_i32), ptr(wg), ptr(conv), B, rows_max, D, G, Kw, stream())
+    if rc == 1:
+        raise SpeechClipHipError(f"packed batches need the windowed positional-conv kernel (D/G in 32/48/64), got D/G = {D // G}")
+    check(rc, "sc_posconv_conv_packed")
+    return conv
+
+
+def posconv_finish_train_packed(x, valid_i32, row_off_i32, conv, bias, B, total_rows, D, G):
+    """posconv_finish_train over packed rows -> (u, s) bf16 [total_rows, D]."""
+    assert x.dtype == bf16 and x.is_contiguous() and x.shape == (total_rows, D) and conv.numel() >= total_rows * D and bias.numel() == D
+    u = torch.empty(total_rows, D, device=x.device, dtype=bf16)
+    s = torch.empty_like(u)
+    check(lib().sc_posconv_finish_train_packed(ptr(x), ptr(valid_i32), ptr(row_off_i32), ptr(conv), ptr(bias), ptr(u), ptr(s), B, total_rows, D, G, stream()),
+          "sc_posconv_finish_train_packed")
+    return u, s
+
+
+def posconv_dgrad_finish_packed(convT, ds, valid_i32, row_off_i32, B, total_rows, D, G):
+    assert ds.dtype == bf16 and ds.is_contiguous() and ds.shape == (total_rows, D) and convT.numel() >= total_rows * D
+    dx = torch.empty(total_rows, D, device=ds.device, dtype=bf16)
+    check(lib().sc_posconv_dgrad_finish_packed(ptr(convT), ptr(ds), ptr(valid_i32), ptr(row_off_i32), ptr(dx), B, total_rows, D, G, stream()),
+          "sc_posconv_dgrad_finish_packed")
+    return dx
+
+
+def reverse_rows_packed_bf16(x, row_off_i32, B, total_rows, D):
+    """out[row_off[b] + rows_b - 1 - t] = x[row_off[b] + t]: time reversal inside every utterance's own rows."""
+    assert x.dtype == bf16 and x.is_contiguous() and x.shape == (total_rows, D)
+    out = torch.empty_like(x)
+    check(lib().sc_reverse_rows_packed_bf16(ptr(x), ptr(row_off_i32), ptr(out), B, total_rows, D, stream()), "sc_reverse_rows_packed_bf16")
+    return out
+
+
+def posconv_pack_gapped(x, lim_i32, row_off_i32, B, total_rows, D, G, gap, lead, slab_rows):
+    """-> bf16 [G, slab_rows, D/G] (+64 slack elements): utterance b's rows t < min(lim[b], rows_b) at slab row lead + row_off[b] + b * gap + t, zeros elsewhere."""
+    assert x.dtype == bf16 and x.is_contiguous() and x.shape == (total_rows, D) and slab_rows >= lead + total_rows + B * gap
+    out = torch.empty(slab_rows * D + 64, device=x.device, dtype=bf16)
+    out[slab_rows * D:].zero_()
+    check(lib().sc_posconv_pack_gapped(ptr(x), ptr(lim_i32), ptr(row_off_i32), ptr(out), B, total_rows, D, G, gap, lead, slab_rows, stream()),
+          "sc_posconv_pack_gapped")
+    return out
+
+
+def conv0_bwd_packed(wav, w, gamma, beta, dy, T0, row_off_i32, row_scale, total_rows, eps=1e-5):
+    """conv0_bwd with dy bf16 [row_scale * total_rows (+ slack), C] on packed rows (utterance b's frames at rows row_scale * row_off[b] ..) -> (dw, dgamma, dbeta);
+    also returns the per-utterance partials f32 [B, C, 12]."""
+    _need_cuda(wav, dy, row_off_i32)
+    B, L = wav.shape
+    C = w.shape[0]
+    assert wav.dtype == torch.float32 and wav.is_contiguous() and w.dtype == torch.float32 and w.is_contiguous() and dy.dtype == bf16 and dy.is_contiguous()
+    assert dy.shape[0] >= row_scale * total_rows and dy.shape[1] == C and row_off_i32.dtype == torch.int32 and row_off_i32.numel() == B + 1
+    part = torch.empty(B, C * 12, device=wav.device, dtype=torch.float32)
+    check(lib().sc_conv0_bwd_packed(ptr(wav), L, ptr(w), ptr(gamma), ptr(beta), ptr(dy), ptr(part), B, C, T0, ptr(row_off_i32), row_scale, eps, stream()),
+          "sc_conv0_bwd_packed")
+    tot = colsum(part).view(C, 12)
+    return tot[:, :10].contiguous(), tot[:, 10].contiguous(), tot[:, 11].contiguous(), part.view(B, C, 12)
+
+
+def conv0_wgrad_packed(wav, du, C, T0, row_off_i32, row_scale, total_rows):
+    """conv0_wgrad with du bf16 [row_scale * total_rows (+ slack), C] on packed rows -> (dw f32 [C, 10], dbias f32 [C], per-utterance partials f32 [B, C, 12])."""
+    _need_cuda(wav, du, row_off_i32)
+    B, L = wav.shape
+    assert wav.dtype == torch.float32 and wav.is_contiguous() and du.dtype == bf16 and du.is_contiguous()
+    assert du.shape[0] >= row_scale * total_rows and du.shape[1] == C and row_off_i32.dtype == torch.int32 and row_off_i32.numel() == B + 1
+    part = torch.empty(B, C * 12, device=wav.device, dtype=torch.float32)
+    check(lib().sc_conv0_wgrad_packed(ptr(wav), L, ptr(du), ptr(part), B, C, T0, ptr(row_off_i32), row_scale, stream()), "sc_conv0_wgrad_packed")
+    tot = colsum(part).view(C, 12)
+    return tot[:, :10].contiguous(), tot[:, 10].contiguous(), part.view(B, C, 12)
 
 
 def gemm_batched2(a, lda, stride_a, stride_a2, w, ldw, stride_w, stride_w2, out, ldc, stride_c, stride_c2, M, N, K, outer, inner):

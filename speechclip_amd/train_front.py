@@ -17,6 +17,14 @@ enters the feature extractor by `feature_grad_mult`, 0.1 in the released base ch
             conv layer 0           sc_conv0_bwd (GroupNorm + GELU + conv from the wave)
 meta["drop"] = dict(features, hidden, seed) applies the two dropouts fairseq has on this stretch in train mode (dropout_input on the projected
 features, F.dropout on hidden state 0) with counter-based masks the backward regenerates.
+
+meta["pack"] = dict(row_off, rows_max, total, scale0) (module/hubert.py: packed_geometry; row_off as B + 1 device ints) runs both nodes on the padding-free
+layout: utterance b owns rows [row_off[b], row_off[b + 1]) at transformer level and scale_l times that range at conv layer l.  Every GEMM, LayerNorm, GELU
+and dropout is row-wise and runs on `total` rows as it is (the dropout masks are indexed by position in the layout in use); the per-utterance kernels
+have packed forms (sc_conv0_fwd_packed, sc_posconv_conv_packed, sc_posconv_finish_train_packed, sc_reverse_rows_packed_bf16, sc_posconv_dgrad_finish_packed,
+sc_posconv_pack_gapped, sc_conv0_bwd_packed / sc_conv0_wgrad_packed).  The gradient stays inside its utterance: dxp is non-zero on rows < valid_b only, and
+output frame F - 1 reaches 64 F + 15 <= 64 (F + 1) layer-0 frames, so the halo row and the rows that read a neighbour's samples (finite junk in the forward)
+meet an exactly zero gradient at every conv level.
 """
 import torch
 
@@ -86,6 +94,32 @@ def posconv_wgrad(du, xp, valid_i32, B, Tp, D, G, Kw):
     return out
 
 
+def posconv_wgrad_packed(du, xp, valid_i32, rows_i32, off_i32, B, total, D, G, Kw):
+    """posconv_wgrad on packed rows (du, xp bf16 [total, D]).  The window slab keeps Kw zero rows between utterances (sc_posconv_pack_gapped) and du takes the
+    same gapped row numbering, so both operands are ONE [rows, cols] matrix and the transpose + split-K GEMM + column-sum chain is posconv_wgrad's; the split
+    count depends on the row count only, so the summation order is fixed for a given batch."""
+    cg = D // G
+    dev = du.device
+    Rg = total + B * Kw                                                 # gapped rows: utterance b starts at row_off[b] + b * Kw
+    S = max(s for s in (16, 8, 4, 2, 1) if s == 1 or Rg >= 512 * s)
+    chunk = -(-Rg // (64 * S)) * 64
+    Ktot = chunk * S
+    xg = ops.posconv_pack_gapped(xp, valid_i32, off_i32, B, total, D, G, Kw, Kw // 2, Ktot + Kw)       # [G, Ktot + Kw, cg], masked input, Kw/2 zero rows in front
+    dug = ops.posconv_pack_gapped(du, rows_i32, off_i32, B, total, D, 1, Kw, 0, Ktot)                  # [Ktot, D], zero rows in the gaps and behind the batch
+    xvT = torch.empty(Kw * cg, Ktot, device=dev, dtype=BF)
+    duT = torch.empty(cg, Ktot, device=dev, dtype=BF)
+    part = torch.empty(S, Kw * cg, cg, device=dev, dtype=torch.float32)
+    out = torch.empty(D, cg, Kw, device=dev, dtype=torch.float32)
+    slab = (Ktot + Kw) * cg
+    for g in range(G):
+        ops.transpose_bf16(xg[g * slab:], cg, 0, Ktot, Kw * cg, 1, rows_padded=Ktot, out=xvT, ld_out=Ktot, stride_out=0)
+        ops.transpose_bf16(dug[g * cg:], D, 0, Ktot, cg, 1, rows_padded=Ktot, out=duT, ld_out=Ktot, stride_out=0)
+        ops.gemm_batched(xvT, Ktot, chunk, duT, chunk, S, part, cg, Kw * cg * cg, None, Kw * cg, cg, chunk, S, ldw=Ktot)
+        tot = part[0] if S == 1 else ops.colsum(part.view(S, Kw * cg * cg)).view(Kw * cg, cg)      # [(tap, in), out]
+        out[g * cg:(g + 1) * cg] = tot.view(Kw, cg, cg).permute(2, 1, 0)
+    return out
+
+
 def _rows_with_slack(n_rows, cols, dev):
     """[n_rows + 8, cols] bf16 whose 8 slack rows are zero (the conv-as-GEMM views over-read / the overlapping tap accumulates into them); the body is
     written in full by the producing GEMM, so it is not filled first."""
@@ -110,22 +144,44 @@ def conv_layer_backward(xin, w, du_i, B, rows_out, dim, k, s, C):
     return dW, dx
 
 
-def posconv_tail_backward(ds, u, xp, valid, pg, pv, B, Tp, d, G, Kw):
+def posconv_tail_backward(ds, u, xp, valid, pg, pv, B, Tp, d, G, Kw, pack=None):
     """s = mask(xp) + gelu(u), u = grouped_conv(mask(xp)) + bias, weight-normalised weight (g, v): gradient ds of s ->
-    (dxp bf16 [B*Tp, d], dg, dv, dbias)."""
+    (dxp bf16 [B*Tp, d], dg, dv, dbias).  pack = (row_off, rows_max, total): all tensors on packed rows ([total, d])."""
     dev = ds.device
     du = ops.gelu_bwd_bf16(u, ds)
     dbias = ops.colsum_bf16(du)
     wfold, norm = _fold_weight_norm(pg, pv)
     _, wg_adj = _pos_operands(wfold, G, Kw)
-    full = ops.dev_ints([Tp] * B, torch.int32, dev)
-    convT = ops.posconv_conv(ops.reverse_rows_bf16(du, B, Tp, d), full, wg_adj, B, Tp, d, G, Kw)
-    dxp = ops.posconv_dgrad_finish(convT, ds, valid, B, Tp, d, G)
-    dwf = posconv_wgrad(du, xp, valid, B, Tp, d, G, Kw)              # gradient of the FOLDED weight
+    if pack is not None:       # the same adjoint, time reversed inside each utterance's own rows_b rows (du is zero beyond them on the padded layout too)
+        off, rows_max, total = pack
+        rows = (off[1:] - off[:-1]).contiguous()
+        convT = ops.posconv_conv_packed(ops.reverse_rows_packed_bf16(du, off, B, total, d), rows, off, wg_adj, B, rows_max, total, d, G, Kw)
+        dxp = ops.posconv_dgrad_finish_packed(convT, ds, valid, off, B, total, d, G)
+        dwf = posconv_wgrad_packed(du, xp, valid, rows, off, B, total, d, G, Kw)
+    else:
+        full = ops.dev_ints([Tp] * B, torch.int32, dev)
+        convT = ops.posconv_conv(ops.reverse_rows_bf16(du, B, Tp, d), full, wg_adj, B, Tp, d, G, Kw)
+        dxp = ops.posconv_dgrad_finish(convT, ds, valid, B, Tp, d, G)
+        dwf = posconv_wgrad(du, xp, valid, B, Tp, d, G, Kw)          # gradient of the FOLDED weight
     v = pv.detach().float()
     dot = (dwf * v).sum(dim=(0, 1), keepdim=True)                     # weight-norm: w = g v / |v|  (norm over dims 0, 1 per tap)
     gf = pg.detach().float()
     return dxp, (dot / norm).to(pg.dtype), (gf / norm * dwf - gf * dot / norm.pow(3) * v).to(pv.dtype), dbias
+
+
+def _front_pack(meta, dev):
+    """(row_off device ints, rows_max, total, scale0) of meta["pack"], or None for the padded layout."""
+    pk = meta.get("pack")
+    if pk is None:
+        return None
+    off = pk["row_off"]
+    off = off if torch.is_tensor(off) else ops.dev_ints(off, torch.int32, dev)
+    return off, int(pk["rows_max"]), int(pk["total"]), int(pk["scale0"])
+
+
+def _zero_rows(n_rows, cols, dev):
+    """conv layer 0's buffer on packed rows: zero-filled with 8 slack rows, as the engine's buf(..., rows + 8, zero=True)."""
+    return torch.zeros(n_rows + 8, cols, device=dev, dtype=BF)
 
 
 class HubertFrontTrainFn(torch.autograd.Function):
@@ -142,17 +198,25 @@ class HubertFrontTrainFn(torch.autograd.Function):
         B = wav.shape[0]
         dev = wav.device
         C = cl[0][0]
-        x = ops.conv0(wav, _f32(c0w).reshape(C, -1), T0, P0, gn_gamma=_f32(gnw), gn_beta=_f32(gnb))
+        pk = _front_pack(meta, dev)
+        if pk is not None:      # packed rows: the conv stack sees ONE utterance of scale0 * total frames (rows are rows)
+            off, rows_max, total, scale0 = pk
+            assert scale0 * Tp == P0
+            Bc, rows = 1, scale0 * total
+            x = ops.conv0_packed(wav, _f32(c0w).reshape(C, -1), T0, off, scale0, rows_max, total, gn_gamma=_f32(gnw), gn_beta=_f32(gnb),
+                                 out=_zero_rows(rows, C, dev))
+        else:
+            Bc, rows = B, P0
+            x = ops.conv0(wav, _f32(c0w).reshape(C, -1), T0, P0, gn_gamma=_f32(gnw), gn_beta=_f32(gnb))
         acts = [x]
-        rows = P0
         for (dim, k, s), w in zip(cl[1:], cws):
             rows //= s
-            y = _rows_with_slack(B * rows, dim, dev)
-            ops.gemm(x, _conv_w16(w), None, ACT_GELU, out=y[:B * rows], M=B * rows, K=k * C, lda=s * C)
+            y = _rows_with_slack(Bc * rows, dim, dev)
+            ops.gemm(x, _conv_w16(w), None, ACT_GELU, out=y[:Bc * rows], M=Bc * rows, K=k * C, lda=s * C)
             acts.append(y)
             x, C = y, dim
-        assert rows == Tp
-        M = B * Tp
+        assert rows == (Tp if pk is None else total)
+        M = Bc * rows
         feats = ops.layernorm(x[:M], _f32(flw), _f32(flb))
         xp = ops.gemm(feats, pw.detach().to(BF).contiguous(), _f32(pb))
         drop = meta.get("drop")          # dict(features, hidden, seed): dropout_input on the projected features, F.dropout on hidden state 0
@@ -160,8 +224,12 @@ class HubertFrontTrainFn(torch.autograd.Function):
             ops.dropout_bf16(xp, drop["features"], drop["seed"] ^ 0x2545F491, out=xp)
         wfold, _ = _fold_weight_norm(pg, pv)
         wg, _ = _pos_operands(wfold, G, Kw)
-        conv = ops.posconv_conv(xp, valid_i32, wg, B, Tp, d, G, Kw)
-        u, s_ = ops.posconv_finish_train(xp, valid_i32, conv, _f32(pbias), B, Tp, d, G)
+        if pk is not None:
+            conv = ops.posconv_conv_packed(xp, valid_i32, off, wg, B, rows_max, total, d, G, Kw)
+            u, s_ = ops.posconv_finish_train_packed(xp, valid_i32, off, conv, _f32(pbias), B, total, d, G)
+        else:
+            conv = ops.posconv_conv(xp, valid_i32, wg, B, Tp, d, G, Kw)
+            u, s_ = ops.posconv_finish_train(xp, valid_i32, conv, _f32(pbias), B, Tp, d, G)
         h0 = ops.layernorm(s_, _f32(elw), _f32(elb), 1e-5)
         if drop is not None and drop["hidden"] > 0:
             h0 = ops.dropout_bf16(h0, drop["hidden"], drop["seed"] ^ 0x61C88647)
@@ -180,8 +248,10 @@ class HubertFrontTrainFn(torch.autograd.Function):
         cws = params[3:9]
         flw, flb, pw, pb, pg, pv, pbias, elw, elb = params[9:]
         B = wav.shape[0]
-        M = B * Tp
         dev = wav.device
+        pk = _front_pack(meta, dev)
+        Bc, Tpc = (B, Tp) if pk is None else (1, pk[2])      # packed rows: the row-wise part runs as ONE utterance of `total` rows
+        M = Bc * Tpc
         valid = ctx.valid
         grads = [None] * N_FRONT
         drop = meta.get("drop")
@@ -191,10 +261,12 @@ class HubertFrontTrainFn(torch.autograd.Function):
         # ---- h0 = [dropout] LN(s)
         ds, grads[16], grads[17] = ops.layernorm_bwd_bf16(s_, dh0, _f32(elw), 1e-5)
         # ---- s = mask(xp) + gelu(u),  u = conv(mask(xp)) + bias
-        dxp, grads[13], grads[14], grads[15] = posconv_tail_backward(ds, u, xp, valid, pg, pv, B, Tp, d, G, Kw)
+        dxp, grads[13], grads[14], grads[15] = posconv_tail_backward(ds, u, xp, valid, pg, pv, B, Tp, d, G, Kw, pack=None if pk is None else pk[:3])
         del ds
         if drop is not None and drop["features"] > 0:
             ops.dropout_bf16(dxp, drop["features"], drop["seed"] ^ 0x2545F491, out=dxp)      # saved xp is the dropped tensor; its gradient takes the same mask
+        if meta.get("trace") is not None:
+            meta["trace"]["dxp"] = dxp
         # ---- xp = [dropout] (feats W^T + b) ; feats = LN(x6)
         dfeats = ops.gemm(dxp, pw.detach().t().to(BF).contiguous())
         grads[11], grads[12] = wgrad(dxp, feats), ops.colsum_bf16(dxp)
@@ -204,25 +276,32 @@ class HubertFrontTrainFn(torch.autograd.Function):
         if mult != 1.0:      # [3P fairseq] GradMultiply on the feature extractor's output
             g = ops.axpy_bf16(torch.zeros_like(g), g, mult)
         # ---- conv layers 6 .. 1
-        rows_out = Tp
+        rows_out = Tpc
         for i in range(6, 0, -1):
             dim, k, s = cl[i]
             C = cl[i - 1][0]
             xin = acts[i - 1]
-            Mi = B * rows_out
+            Mi = Bc * rows_out
             rows_in = rows_out * s
             w16 = _conv_w16(cws[i - 1])
             upre = ops.gemm(xin, w16, None, ACT_NONE, M=Mi, K=k * C, lda=s * C)        # pre-activation, recomputed
             du_i = ops.gelu_bwd_bf16(upre, g)
             del upre
-            grads[3 + i - 1], dx = conv_layer_backward(xin, cws[i - 1], du_i, B, rows_out, dim, k, s, C)
-            g = dx[:B * rows_in]
+            grads[3 + i - 1], dx = conv_layer_backward(xin, cws[i - 1], du_i, Bc, rows_out, dim, k, s, C)
+            g = dx[:Bc * rows_in]
             rows_out = rows_in
             del du_i
-        assert rows_out == P0
+            if meta.get("trace") is not None:      # tests: the input gradient of every conv level
+                meta["trace"]["dx%d" % (i - 1)] = g
+        assert rows_out == (P0 if pk is None else pk[3] * pk[2])
         # ---- conv layer 0 from the wave
         C0 = cl[0][0]
-        dw0, dgn, dbn = ops.conv0_bwd(wav, _f32(c0w).reshape(C0, -1), _f32(gnw), _f32(gnb), g.contiguous(), T0, P0)
+        if pk is not None:
+            dw0, dgn, dbn, part = ops.conv0_bwd_packed(wav, _f32(c0w).reshape(C0, -1), _f32(gnw), _f32(gnb), g.contiguous(), T0, pk[0], pk[3], pk[2])
+            if meta.get("trace") is not None:
+                meta["trace"]["conv0_part"] = part
+        else:
+            dw0, dgn, dbn = ops.conv0_bwd(wav, _f32(c0w).reshape(C0, -1), _f32(gnw), _f32(gnb), g.contiguous(), T0, P0)
         grads[0], grads[1], grads[2] = dw0.view_as(c0w), dgn, dbn
         return (None, None, None, *grads)
 
@@ -259,31 +338,42 @@ class HubertFrontLNTrainFn(torch.autograd.Function):
             wav = ops.wave_layernorm(wav.contiguous(), lens_i32)
         C = cl[0][0]
         w0, b0, g0, be0 = params[:4]
-        u = ops.conv0(wav, _f32(w0).reshape(C, -1), T0, P0, bias=_f32(b0))                  # conv + bias; rows >= T0 are zeros
+        pk = _front_pack(meta, dev)
+        if pk is not None:
+            off, rows_max, total, scale0 = pk
+            assert scale0 * Tp == P0
+            Bc, rows = 1, scale0 * total
+            u = ops.conv0_packed(wav, _f32(w0).reshape(C, -1), T0, off, scale0, rows_max, total, bias=_f32(b0), out=_zero_rows(rows, C, dev))
+        else:
+            Bc, rows = B, P0
+            u = ops.conv0(wav, _f32(w0).reshape(C, -1), T0, P0, bias=_f32(b0))              # conv + bias; rows >= T0 are zeros
         pre, acts = [u], []
         x = torch.zeros_like(u)
-        ops.layernorm(u[:B * P0], _f32(g0), _f32(be0), gelu=True, out=x[:B * P0])
+        ops.layernorm(u[:Bc * rows], _f32(g0), _f32(be0), gelu=True, out=x[:Bc * rows])
         acts.append(x)
-        rows = P0
         for li, (dim, k, s) in enumerate(cl[1:], start=1):
             w, b, g, be = params[4 * li:4 * li + 4]
             rows //= s
-            u = _rows_with_slack(B * rows, dim, dev)
-            ops.gemm(x, _conv_w16(w), _f32(b), ACT_NONE, out=u[:B * rows], M=B * rows, K=k * C, lda=s * C)
-            y = _rows_with_slack(B * rows, dim, dev)
-            ops.layernorm(u[:B * rows], _f32(g), _f32(be), gelu=True, out=y[:B * rows])
+            u = _rows_with_slack(Bc * rows, dim, dev)
+            ops.gemm(x, _conv_w16(w), _f32(b), ACT_NONE, out=u[:Bc * rows], M=Bc * rows, K=k * C, lda=s * C)
+            y = _rows_with_slack(Bc * rows, dim, dev)
+            ops.layernorm(u[:Bc * rows], _f32(g), _f32(be), gelu=True, out=y[:Bc * rows])
             pre.append(u)
             acts.append(y)
             x, C = y, dim
-        assert rows == Tp
-        M = B * Tp
+        assert rows == (Tp if pk is None else total)
+        M = Bc * rows
         flw, flb, pw, pb, pg, pv, pbias = params[28:]
         feats = ops.layernorm(x[:M], _f32(flw), _f32(flb))
         xp = ops.gemm(feats, pw.detach().to(BF).contiguous(), _f32(pb))
         wfold, _ = _fold_weight_norm(pg, pv)
         wg, _ = _pos_operands(wfold, G, Kw)
-        conv = ops.posconv_conv(xp, valid_i32, wg, B, Tp, d, G, Kw)
-        upos, s_ = ops.posconv_finish_train(xp, valid_i32, conv, _f32(pbias), B, Tp, d, G)
+        if pk is not None:
+            conv = ops.posconv_conv_packed(xp, valid_i32, off, wg, B, rows_max, total, d, G, Kw)
+            upos, s_ = ops.posconv_finish_train_packed(xp, valid_i32, off, conv, _f32(pbias), B, total, d, G)
+        else:
+            conv = ops.posconv_conv(xp, valid_i32, wg, B, Tp, d, G, Kw)
+            upos, s_ = ops.posconv_finish_train(xp, valid_i32, conv, _f32(pbias), B, Tp, d, G)
         ctx.meta = meta
         ctx.valid = valid_i32
         ctx.save_for_backward(wav, *pre, *acts, feats, xp, upos, *[p.detach() for p in params])
@@ -297,22 +387,26 @@ class HubertFrontLNTrainFn(torch.autograd.Function):
         wav, pre, acts, (feats, xp, upos), params = t[0], t[1:8], t[8:15], t[15:18], t[18:]
         flw, flb, pw, pb, pg, pv, pbias = params[28:]
         B = wav.shape[0]
-        M = B * Tp
+        pk = _front_pack(meta, wav.device)
+        Bc, Tpc = (B, Tp) if pk is None else (1, pk[2])
+        M = Bc * Tpc
         grads = [None] * N_FRONT_LN
         ds = dh0.to(BF).contiguous()
-        dxp, grads[32], grads[33], grads[34] = posconv_tail_backward(ds, upos, xp, ctx.valid, pg, pv, B, Tp, d, G, Kw)
+        dxp, grads[32], grads[33], grads[34] = posconv_tail_backward(ds, upos, xp, ctx.valid, pg, pv, B, Tp, d, G, Kw, pack=None if pk is None else pk[:3])
+        if meta.get("trace") is not None:
+            meta["trace"]["dxp"] = dxp
         dfeats = ops.gemm(dxp, pw.detach().t().to(BF).contiguous())
         grads[30], grads[31] = wgrad(dxp, feats), ops.colsum_bf16(dxp)
         g, grads[28], grads[29] = ops.layernorm_bwd_bf16(acts[6][:M], dfeats, _f32(flw), 1e-5)
         mult = float(meta["grad_mult"])
         if mult != 1.0:
             g = ops.axpy_bf16(torch.zeros_like(g), g, mult)
-        rows_out = Tp
+        rows_out = Tpc
         for li in range(6, -1, -1):
             dim, k, s = cl[li]
             w, b, gam, bet = params[4 * li:4 * li + 4]
             rows = rows_out
-            u = pre[li][:B * rows]
+            u = pre[li][:Bc * rows]
             z = ops.layernorm(u, _f32(gam), _f32(bet))                                        # the GELU's argument, recomputed
             dz = ops.gelu_bwd_bf16(z, g.contiguous())
             del z
@@ -320,12 +414,19 @@ class HubertFrontLNTrainFn(torch.autograd.Function):
             del dz
             if li == 0:
                 C0 = cl[0][0]
-                dw0, db0 = ops.conv0_wgrad(wav, du.contiguous(), C0, T0, P0)
+                if pk is not None:
+                    dw0, db0, part = ops.conv0_wgrad_packed(wav, du.contiguous(), C0, T0, pk[0], pk[3], pk[2])
+                    if meta.get("trace") is not None:
+                        meta["trace"]["conv0_part"] = part
+                else:
+                    dw0, db0 = ops.conv0_wgrad(wav, du.contiguous(), C0, T0, P0)
                 grads[0], grads[1] = dw0.view_as(w), db0
                 break
             C = cl[li - 1][0]
             grads[4 * li + 1] = ops.colsum_bf16(du)
-            grads[4 * li], dx = conv_layer_backward(acts[li - 1], w, du, B, rows_out, dim, k, s, C)
+            grads[4 * li], dx = conv_layer_backward(acts[li - 1], w, du, Bc, rows_out, dim, k, s, C)
             rows_out = rows_out * s
-            g = dx[:B * rows_out]
+            g = dx[:Bc * rows_out]
+            if meta.get("trace") is not None:
+                meta["trace"]["dx%d" % (li - 1)] = g
         return (None, None, None, None, *grads)
