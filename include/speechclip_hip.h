@@ -363,13 +363,18 @@ int sc_transpose_bf16(const void* in, int64_t ld_in, int64_t stride_in, void* ou
  * layer_norm and the positional conv as well (avssl/module/speech_encoder_plus.py:399-401: freeze_model is not called; [3P fairseq]
  * HubertModel.forward_features scales the extractor's gradient by feature_grad_mult).  GEMM-shaped parts reuse sc_gemm_bf16 / sc_gemm_bf16_batched /
  * sc_posconv_conv (speechclip_amd/train_front.py); these entries are the rest:
- *   sc_posconv_finish_train: training forward of the positional-conv tail (speech_encoder_plus.py:35-37): u = conv + bias regrouped from
- *     [B, G, Tp, D/G] to bf16 [B*Tp, D], s = mask(x) + gelu(u) (bf16; the LayerNorm after it runs as sc_layernorm) -- both kept for the backward.
+ * Each operation is ONE kernel serving both row layouts: uniform rows (B utterances of Tp rows) are the packed layout with row_off[b] = b * Tp and
+ * rows_b = Tp.  The entries below take the uniform layout; their *_packed forms (further down) take row_off and forward into the same code.
+ *   sc_posconv_finish_train: training forward of the positional-conv tail (speech_encoder_plus.py:35-37): u = conv + bias regrouped from the conv slabs
+ *     (utterance b = [G][rows_b][D/G] at element row_off[b] * D; uniform: [B, G, Tp, D/G]) to bf16 [rows, D], s = mask(x) + gelu(u) (bf16, the GELU taken
+ *     at the bf16-rounded u; the LayerNorm after it runs as sc_layernorm) -- both kept for the backward.  D/G a multiple of 4 (8 elements per thread when
+ *     it is a multiple of 8, else 4).
  *   sc_posconv_dgrad_finish: dx = mask(ds + time-reversed regroup of convT), convT = sc_posconv_conv of the time-reversed du with the in/out
- *     channel-swapped weights (the adjoint of "pad Kw/2, drop the last output" is the same conv on the reversed sequence).
- *   sc_reverse_rows_bf16: out[b, t, :] = in[b, T-1-t, :].
+ *     channel-swapped weights (the adjoint of "pad Kw/2, drop the last output" is the same conv on the reversed sequence); rows >= valid[b] are zeros.
+ *   sc_reverse_rows_bf16: out[b, t, :] = in[b, T-1-t, :] (packed: inside each utterance's own rows).
  *   sc_conv0_bwd: conv layer 0 = Conv1d(1 -> C, k 10, s 5, no bias) -> GroupNorm(C groups, statistics over the T0 frames) -> GELU, from the wave:
- *     dy bf16 [B, P, C] -> part f32 [B, C, 12] = per-utterance (dw[0..9], dgamma, dbeta); sum over B for the parameter gradients. */
+ *     dy bf16 [B, P, C] -> part f32 [B, C, 12] = per-utterance (dw[0..9], dgamma, dbeta); sum over B for the parameter gradients.
+ * Zero rows (B * Tp == 0, B == 0) return 0 without a launch. */
 int sc_posconv_finish_train(const void* x, const int32_t* valid, const void* conv, const float* bias, void* u, void* s, int B, int Tp, int D, int G,
                             void* stream);
 int sc_posconv_dgrad_finish(const void* convT, const void* ds, const int32_t* valid, void* dx, int B, int Tp, int D, int G, void* stream);
@@ -417,12 +422,15 @@ int sc_cls_pool_dz(const float* pp, const float* ds, const float* dzbar, const f
  *                            The encoder passes halo = 1: the last row of every utterance is the receptive-field halo (inexact, reads the
  *                            neighbouring utterance's samples) and is not exposed; frames >= max(valid_b, feat_len_b) are zeros.
  * Whole-encoder training on packed rows (speechclip_amd/train_front.py) adds the backward's per-utterance kernels; none of them uses atomics:
- *   sc_conv0_bwd_packed / sc_conv0_wgrad_packed   sc_conv0_bwd / sc_conv0_wgrad with dy / du read at rows row_scale * row_off[b] + t and taken as zero for
- *                            t >= row_scale * rows_b.  The wave stays the padded [B, ld]; the GroupNorm statistics and every sum of its backward run over all
- *                            T0 frames of the padded length (frames the layout does not materialise carry no dy but still enter the mean-subtraction terms).
- *   sc_posconv_finish_train_packed / sc_posconv_dgrad_finish_packed / sc_reverse_rows_packed_bf16   the packed forms of the three elementwise kernels over
- *                            sc_posconv_conv_packed's slab layout; the time reversal runs inside each utterance's own rows.  dx = mask(ds + conv^T du) with
- *                            convT = sc_posconv_conv_packed(reversed du, valid = rows_b, swapped weights); every row of u / s / dx / out is written.
+ *   sc_conv0_bwd_packed / sc_conv0_wgrad_packed   the kernels of sc_conv0_bwd / sc_conv0_wgrad with dy / du read at rows row_scale * row_off[b] + t and taken
+ *                            as zero for t >= row_scale * rows_b (uniform: row b * P + t, and P >= T0 makes the limit T0).  The wave stays the padded [B, ld];
+ *                            the GroupNorm statistics and every sum of its backward run over all T0 frames of the padded length (frames the layout does not
+ *                            materialise carry no dy but still enter the mean-subtraction terms).
+ *   sc_posconv_finish_train_packed / sc_posconv_dgrad_finish_packed / sc_reverse_rows_packed_bf16   the kernels of the three uniform entries with the row's
+ *                            utterance found in row_off (binary search) instead of by division, over sc_posconv_conv_packed's slab layout; with
+ *                            row_off[b] = b * Tp they give the uniform entries' output bit for bit.  dx = mask(ds + conv^T du) with convT =
+ *                            sc_posconv_conv_packed(reversed du, valid = rows_b, swapped weights); every row of u / s / dx / out is written.  They need
+ *                            D/G (D for the reversal) a multiple of 8, B > 0, total_rows > 0 and row_off.
  *   sc_posconv_pack_gapped   out bf16 [G][slab_rows][D/G]: row lead + row_off[b] + b * gap + t of group g = row row_off[b] + t of x for t < min(lim[b], rows_b),
  *                            zeros everywhere else (slab_rows >= lead + total_rows + B * gap; every row written).  With gap = Kw a window of Kw rows never sees
  *                            two utterances, so the positional conv's dW is ONE [rows, cols] product: (x, lim = valid, lead = Kw/2) is its sliding-window

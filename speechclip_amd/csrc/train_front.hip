@@ -10,12 +10,14 @@
 //   sc_conv0_bwd              conv layer 0 (Conv1d(1 -> C, k=10, s=5, no bias) -> GroupNorm(C groups) over time -> GELU) backward from the wave:
 //                             per-(b, c) partial gradients of the conv weight [10], gamma and beta (summed over b by sc_colsum)
 // Packed (padding-free) batches -- utterance b owns rows [row_off[b], row_off[b + 1]) at transformer level and row_scale times that range at conv
-// layer 0 (module/hubert.py: packed_geometry) -- have their own forms of the per-utterance kernels; every GEMM-shaped part is row-wise and runs as it is:
+// layer 0 (module/hubert.py: packed_geometry) -- run on the SAME kernels: the padded layout is the packed one with row_off[b] = b * Tp and rows_b = Tp, so
+// every operation is one kernel and one host _impl, and its two entries (uniform / *_packed, which takes row_off) are thin forwards into it.  Every
+// GEMM-shaped part is row-wise and runs as it is.
 //   sc_conv0_bwd_packed / sc_conv0_wgrad_packed   dy / du read at rows row_scale * row_off[b] + t, zero for frames the layout does not materialise
-//                             (the GroupNorm sums still run over all T0 frames of the padded length)
-//   sc_posconv_finish_train_packed / sc_posconv_dgrad_finish_packed / sc_reverse_rows_packed_bf16   the elementwise kernels over sc_posconv_conv_packed's
-//                             slab layout ([G][rows_b][cg] at element row_off[b] * D), time reversed inside each utterance's own rows
-//   sc_posconv_pack_gapped    the window slab of the weight gradient with Kw zero rows between utterances, so that dW stays ONE [rows, cols] product
+//                             (the GroupNorm sums still run over all T0 frames of the padded length); uniform: rows b * P + t, all T0 frames
+//   sc_posconv_finish_train_packed / sc_posconv_dgrad_finish_packed / sc_reverse_rows_packed_bf16   over sc_posconv_conv_packed's slab layout
+//                             ([G][rows_b][cg] at element row_off[b] * D, = [B, G, Tp, cg] on uniform rows), time reversed inside each utterance's own rows
+//   sc_posconv_pack_gapped    (packed only) the window slab of the weight gradient with Kw zero rows between utterances, so that dW stays ONE [rows, cols] product
 #include "common.h"
 #include "../../include/speechclip_hip.h"
 
@@ -25,59 +27,108 @@ __device__ __forceinline__ float gelu_grad(float x) {
     return 0.5f * (1.0f + fast_erf(x * 0.70710678118654752f)) + x * 0.3989422804014327f * __expf(-0.5f * x * x);
 }
 
-// u[row, e] = conv[b, g, t, ci] + bias[e];  s[row, e] = (t < valid[b] ? x[row, e] : 0) + gelu(u)
-__global__ __launch_bounds__(256) void posconv_finish_train_kernel(const bf16_t* __restrict__ x, const int32_t* __restrict__ valid, const bf16_t* __restrict__ conv,
-                                                                   const float* __restrict__ bias, bf16_t* __restrict__ u, bf16_t* __restrict__ s, int B, int Tp,
-                                                                   int D, int G) {
-    const int64_t idx = ((int64_t)blockIdx.x * 256 + threadIdx.x) * 4;
-    if (idx >= (int64_t)B * Tp * D) return;
-    const int64_t row = idx / D;
-    const int e = (int)(idx - row * D);
-    const int b = (int)(row / Tp), t = (int)(row - (int64_t)b * Tp);
-    const int cg = D / G, g = e / cg, ci = e - g * cg;
-    const uint2 cv = *(const uint2*)(conv + (((int64_t)b * G + g) * Tp + t) * cg + ci);
-    float xv[4] = {0.f, 0.f, 0.f, 0.f};
-    if (t < valid[b]) {
-        const uint2 xx = *(const uint2*)(x + idx);
-        xv[0] = lo2f(xx.x); xv[1] = hi2f(xx.x); xv[2] = lo2f(xx.y); xv[3] = hi2f(xx.y);
-    }
-    const float uv[4] = {lo2f(cv.x) + bias[e], hi2f(cv.x) + bias[e + 1], lo2f(cv.y) + bias[e + 2], hi2f(cv.y) + bias[e + 3]};
-    uint2 uo, so;
-    uo.x = pack2bf(uv[0], uv[1]); uo.y = pack2bf(uv[2], uv[3]);
-    // gelu of the bf16-ROUNDED pre-activation: the backward differentiates gelu at exactly the value it is handed
-    const float ur[4] = {lo2f(uo.x), hi2f(uo.x), lo2f(uo.y), hi2f(uo.y)};
-    so.x = pack2bf(xv[0] + gelu_erf_precise(ur[0]), xv[1] + gelu_erf_precise(ur[1]));
-    so.y = pack2bf(xv[2] + gelu_erf_precise(ur[2]), xv[3] + gelu_erf_precise(ur[3]));
-    *(uint2*)(u + idx) = uo;
-    *(uint2*)(s + idx) = so;
+// ------------------------------------------------------------------------------------------------ row-streaming kernels, padded and packed rows
+// One kernel per operation.  A thread owns V adjacent channels of one row (V = 8: one 16-byte load / store per tensor, when the group width D/G is a
+// multiple of 8; else V = 4; either way the V channels lie in one group).  The row's utterance b, its first row r0 and its row count rows_b come from
+// row_off by binary search on packed rows and from b = row / Tp, r0 = b * Tp, rows_b = Tp on uniform rows (the packed layout with row_off[b] = b * Tp);
+// everything after that is one body.  The conv slab of utterance b is [G][rows_b][cg] at element r0 * D, which is [B, G, Tp, cg] on uniform rows.
+__device__ __forceinline__ int pk_find(const int32_t* __restrict__ off, int B, int64_t row) {
+    int lo = 0, hi = B;
+    while (hi - lo > 1) { const int mid = (lo + hi) >> 1; if ((int64_t)off[mid] <= row) lo = mid; else hi = mid; }
+    return lo;
+}
+template <bool PACKED>
+__device__ __forceinline__ int row_owner(const int32_t* __restrict__ off, int B, int Tp, int64_t row, int64_t& r0, int& rows_b) {
+    if (PACKED) { const int b = pk_find(off, B, row); r0 = off[b]; rows_b = off[b + 1] - off[b]; return b; }
+    const int b = (int)(row / Tp);
+    r0 = (int64_t)b * Tp; rows_b = Tp;
+    return b;
+}
+template <int V> struct alignas(2 * V) bfv { uint32_t w[V / 2]; };      // V bf16 values: uint2 / uint4
+template <int V> __device__ __forceinline__ bfv<V> ld_bfv(const bf16_t* p) { return *(const bfv<V>*)p; }
+template <int V> __device__ __forceinline__ void unpack_bfv(const bfv<V> v, float (&f)[V]) {
+#pragma unroll
+    for (int i = 0; i < V / 2; ++i) { f[2 * i] = lo2f(v.w[i]); f[2 * i + 1] = hi2f(v.w[i]); }
+}
+template <int V> __device__ __forceinline__ bfv<V> pack_bfv(const float (&f)[V]) {
+    bfv<V> v;
+#pragma unroll
+    for (int i = 0; i < V / 2; ++i) v.w[i] = pack2bf(f[2 * i], f[2 * i + 1]);
+    return v;
 }
 
-// dx[row, e] = t < valid[b] ? ds[row, e] + convT[b, g, Tp-1-t, ci] : 0
-__global__ __launch_bounds__(256) void posconv_dgrad_finish_kernel(const bf16_t* __restrict__ convT, const bf16_t* __restrict__ ds, const int32_t* __restrict__ valid,
-                                                                   bf16_t* __restrict__ dx, int B, int Tp, int D, int G) {
-    const int64_t idx = ((int64_t)blockIdx.x * 256 + threadIdx.x) * 4;
-    if (idx >= (int64_t)B * Tp * D) return;
+// u[row, e] = conv[b][g][t][ci] + bias[e];  s[row, e] = (t < valid[b] ? x[row, e] : 0) + gelu(u)
+template <int V, bool PACKED>
+__global__ __launch_bounds__(256) void posconv_finish_train_kernel(const bf16_t* __restrict__ x, const int32_t* __restrict__ valid, const bf16_t* __restrict__ conv,
+                                                                   const float* __restrict__ bias, bf16_t* __restrict__ u, bf16_t* __restrict__ s,
+                                                                   const int32_t* __restrict__ row_off, int B, int Tp, int64_t rows, int D, int G) {
+    const int64_t idx = ((int64_t)blockIdx.x * 256 + threadIdx.x) * V;
+    if (idx >= rows * D) return;
     const int64_t row = idx / D;
     const int e = (int)(idx - row * D);
-    const int b = (int)(row / Tp), t = (int)(row - (int64_t)b * Tp);
-    uint2 o = make_uint2(0u, 0u);
+    int64_t r0;
+    int rows_b;
+    const int b = row_owner<PACKED>(row_off, B, Tp, row, r0, rows_b);
+    const int t = (int)(row - r0);
+    const int cg = D / G, g = e / cg, ci = e - g * cg;
+    float cv[V], xv[V], uv[V], ur[V], sv[V];
+    unpack_bfv<V>(ld_bfv<V>(conv + (r0 * G + (int64_t)g * rows_b + t) * cg + ci), cv);
+    bfv<V> xx = {};
+    if (t < valid[b]) xx = ld_bfv<V>(x + idx);
+    unpack_bfv<V>(xx, xv);
+#pragma unroll
+    for (int i = 0; i < V; i += 4) {
+        const f32x4_t bv = *(const f32x4_t*)(bias + e + i);
+#pragma unroll
+        for (int j = 0; j < 4; ++j) uv[i + j] = cv[i + j] + bv[j];
+    }
+    const bfv<V> uo = pack_bfv<V>(uv);
+    unpack_bfv<V>(uo, ur);              // gelu of the bf16-ROUNDED pre-activation: the backward differentiates gelu at exactly the value it is handed
+#pragma unroll
+    for (int i = 0; i < V; ++i) sv[i] = xv[i] + gelu_erf_precise(ur[i]);
+    *(bfv<V>*)(u + idx) = uo;
+    *(bfv<V>*)(s + idx) = pack_bfv<V>(sv);
+}
+
+// dx[row, e] = t < valid[b] ? ds[row, e] + convT[b][g][rows_b - 1 - t][ci] : 0  (convT: the grouped conv of the time-reversed du)
+template <int V, bool PACKED>
+__global__ __launch_bounds__(256) void posconv_dgrad_finish_kernel(const bf16_t* __restrict__ convT, const bf16_t* __restrict__ ds, const int32_t* __restrict__ valid,
+                                                                   bf16_t* __restrict__ dx, const int32_t* __restrict__ row_off, int B, int Tp, int64_t rows,
+                                                                   int D, int G) {
+    const int64_t idx = ((int64_t)blockIdx.x * 256 + threadIdx.x) * V;
+    if (idx >= rows * D) return;
+    const int64_t row = idx / D;
+    const int e = (int)(idx - row * D);
+    int64_t r0;
+    int rows_b;
+    const int b = row_owner<PACKED>(row_off, B, Tp, row, r0, rows_b);
+    const int t = (int)(row - r0);
+    bfv<V> o = {};
     if (t < valid[b]) {
         const int cg = D / G, g = e / cg, ci = e - g * cg;
-        const uint2 cv = *(const uint2*)(convT + (((int64_t)b * G + g) * Tp + (Tp - 1 - t)) * cg + ci);
-        const uint2 dv = *(const uint2*)(ds + idx);
-        o.x = pack2bf(lo2f(cv.x) + lo2f(dv.x), hi2f(cv.x) + hi2f(dv.x));
-        o.y = pack2bf(lo2f(cv.y) + lo2f(dv.y), hi2f(cv.y) + hi2f(dv.y));
+        float cv[V], dv[V], ov[V];
+        unpack_bfv<V>(ld_bfv<V>(convT + (r0 * G + (int64_t)g * rows_b + (rows_b - 1 - t)) * cg + ci), cv);
+        unpack_bfv<V>(ld_bfv<V>(ds + idx), dv);
+#pragma unroll
+        for (int i = 0; i < V; ++i) ov[i] = cv[i] + dv[i];
+        o = pack_bfv<V>(ov);
     }
-    *(uint2*)(dx + idx) = o;
+    *(bfv<V>*)(dx + idx) = o;
 }
 
-__global__ __launch_bounds__(256) void reverse_rows_kernel(const bf16_t* __restrict__ in, bf16_t* __restrict__ out, int B, int T, int D) {
-    const int64_t idx = ((int64_t)blockIdx.x * 256 + threadIdx.x) * 4;
-    if (idx >= (int64_t)B * T * D) return;
+// out[r0 + rows_b - 1 - t, :] = in[r0 + t, :]: time reversal inside every utterance's own rows
+template <int V, bool PACKED>
+__global__ __launch_bounds__(256) void reverse_rows_kernel(const bf16_t* __restrict__ in, bf16_t* __restrict__ out, const int32_t* __restrict__ row_off, int B,
+                                                           int Tp, int64_t rows, int D) {
+    const int64_t idx = ((int64_t)blockIdx.x * 256 + threadIdx.x) * V;
+    if (idx >= rows * D) return;
     const int64_t row = idx / D;
     const int e = (int)(idx - row * D);
-    const int b = (int)(row / T), t = (int)(row - (int64_t)b * T);
-    *(uint2*)(out + ((int64_t)b * T + (T - 1 - t)) * D + e) = *(const uint2*)(in + idx);
+    int64_t r0;
+    int rows_b;
+    row_owner<PACKED>(row_off, B, Tp, row, r0, rows_b);
+    const int t = (int)(row - r0);
+    *(bfv<V>*)(out + (r0 + (rows_b - 1 - t)) * D + e) = ld_bfv<V>(in + idx);
 }
 
 // conv layer 0 backward.  Block = (b, 64 channels); lane = channel, the 4 waves split the frames.  Three sweeps over the T0 frames, the conv
@@ -196,83 +247,6 @@ __global__ __launch_bounds__(256) void conv0_wgrad_kernel(const float* __restric
     }
 }
 
-// ------------------------------------------------------------------------------------------------ packed (padding-free) batches
-// Row-streaming kernels over packed rows: a thread owns 8 adjacent channels (one 16-byte load / store per tensor; cg % 8 == 0 keeps them in one group).
-// The owning utterance of a row is found by binary search in row_off (row_off[b] <= row < row_off[b + 1]), as posconv_finish_kernel does.
-__device__ __forceinline__ int pk_find(const int32_t* __restrict__ off, int B, int64_t row) {
-    int lo = 0, hi = B;
-    while (hi - lo > 1) { const int mid = (lo + hi) >> 1; if ((int64_t)off[mid] <= row) lo = mid; else hi = mid; }
-    return lo;
-}
-__device__ __forceinline__ void pk_unpack8(const uint4 v, float (&f)[8]) {
-    f[0] = lo2f(v.x); f[1] = hi2f(v.x); f[2] = lo2f(v.y); f[3] = hi2f(v.y); f[4] = lo2f(v.z); f[5] = hi2f(v.z); f[6] = lo2f(v.w); f[7] = hi2f(v.w);
-}
-__device__ __forceinline__ uint4 pk_pack8(const float (&f)[8]) {
-    return make_uint4(pack2bf(f[0], f[1]), pack2bf(f[2], f[3]), pack2bf(f[4], f[5]), pack2bf(f[6], f[7]));
-}
-
-// posconv_finish_train_kernel over packed rows: conv slab of utterance b = [G][rows_b][cg] at element row_off[b] * D
-__global__ __launch_bounds__(256) void posconv_finish_train_packed_kernel(const bf16_t* __restrict__ x, const int32_t* __restrict__ valid,
-                                                                          const int32_t* __restrict__ row_off, const bf16_t* __restrict__ conv,
-                                                                          const float* __restrict__ bias, bf16_t* __restrict__ u, bf16_t* __restrict__ s, int B,
-                                                                          int64_t total_rows, int D, int G) {
-    const int64_t idx = ((int64_t)blockIdx.x * 256 + threadIdx.x) * 8;
-    if (idx >= total_rows * D) return;
-    const int64_t row = idx / D;
-    const int e = (int)(idx - row * D);
-    const int b = pk_find(row_off, B, row);
-    const int r0 = row_off[b], t = (int)(row - r0), rows_b = row_off[b + 1] - r0;
-    const int cg = D / G, g = e / cg, ci = e - g * cg;
-    float cv[8], xv[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f}, uv[8], sv[8];
-    pk_unpack8(*(const uint4*)(conv + ((int64_t)r0 * G + (int64_t)g * rows_b + t) * cg + ci), cv);
-    if (t < valid[b]) pk_unpack8(*(const uint4*)(x + idx), xv);
-    const f32x4_t b0 = *(const f32x4_t*)(bias + e), b1 = *(const f32x4_t*)(bias + e + 4);
-#pragma unroll
-    for (int i = 0; i < 8; ++i) uv[i] = cv[i] + (i < 4 ? b0[i] : b1[i - 4]);
-    const uint4 uo = pk_pack8(uv);
-    float ur[8];
-    pk_unpack8(uo, ur);               // gelu of the bf16-ROUNDED pre-activation, as the padded kernel
-#pragma unroll
-    for (int i = 0; i < 8; ++i) sv[i] = xv[i] + gelu_erf_precise(ur[i]);
-    *(uint4*)(u + idx) = uo;
-    *(uint4*)(s + idx) = pk_pack8(sv);
-}
-
-// dx[row, e] = t < valid[b] ? ds[row, e] + convT[b][g][rows_b - 1 - t][ci] : 0 (convT: sc_posconv_conv_packed of the per-utterance reversed du)
-__global__ __launch_bounds__(256) void posconv_dgrad_finish_packed_kernel(const bf16_t* __restrict__ convT, const bf16_t* __restrict__ ds,
-                                                                          const int32_t* __restrict__ valid, const int32_t* __restrict__ row_off,
-                                                                          bf16_t* __restrict__ dx, int B, int64_t total_rows, int D, int G) {
-    const int64_t idx = ((int64_t)blockIdx.x * 256 + threadIdx.x) * 8;
-    if (idx >= total_rows * D) return;
-    const int64_t row = idx / D;
-    const int e = (int)(idx - row * D);
-    const int b = pk_find(row_off, B, row);
-    const int r0 = row_off[b], t = (int)(row - r0), rows_b = row_off[b + 1] - r0;
-    uint4 o = make_uint4(0u, 0u, 0u, 0u);
-    if (t < valid[b]) {
-        const int cg = D / G, g = e / cg, ci = e - g * cg;
-        float cv[8], dv[8], ov[8];
-        pk_unpack8(*(const uint4*)(convT + ((int64_t)r0 * G + (int64_t)g * rows_b + (rows_b - 1 - t)) * cg + ci), cv);
-        pk_unpack8(*(const uint4*)(ds + idx), dv);
-#pragma unroll
-        for (int i = 0; i < 8; ++i) ov[i] = cv[i] + dv[i];
-        o = pk_pack8(ov);
-    }
-    *(uint4*)(dx + idx) = o;
-}
-
-// out[row_off[b] + rows_b - 1 - t, :] = in[row_off[b] + t, :]
-__global__ __launch_bounds__(256) void reverse_rows_packed_kernel(const bf16_t* __restrict__ in, const int32_t* __restrict__ row_off, bf16_t* __restrict__ out,
-                                                                  int B, int64_t total_rows, int D) {
-    const int64_t idx = ((int64_t)blockIdx.x * 256 + threadIdx.x) * 8;
-    if (idx >= total_rows * D) return;
-    const int64_t row = idx / D;
-    const int e = (int)(idx - row * D);
-    const int b = pk_find(row_off, B, row);
-    const int r0 = row_off[b], t = (int)(row - r0), rows_b = row_off[b + 1] - r0;
-    *(uint4*)(out + ((int64_t)r0 + (rows_b - 1 - t)) * D + e) = *(const uint4*)(in + idx);
-}
-
 // out[g][lead + row_off[b] + b * gap + t][c] = t < min(lim[b], rows_b) ? x[row_off[b] + t][g * cg + c] : 0; every other row of the [G][slab_rows][cg] slab is zero.
 // Utterance b starts at gapped row row_off[b] + b * gap: with gap = Kw zero rows between neighbours a window of Kw rows never sees two utterances.
 __global__ __launch_bounds__(256) void posconv_pack_gapped_kernel(const bf16_t* __restrict__ x, const int32_t* __restrict__ lim, const int32_t* __restrict__ row_off,
@@ -296,124 +270,134 @@ __global__ __launch_bounds__(256) void posconv_pack_gapped_kernel(const bf16_t* 
 
 }  // namespace
 
-extern "C" int sc_conv0_wgrad(const float* wav, int64_t ld, const void* du, float* part, int B, int C, int T0, int P, void* stream) {
-    SC_CHECK_ARG(wav && du && part, "sc_conv0_wgrad: null operand");
-    SC_CHECK_ARG(C % 64 == 0 && B <= 65535, "sc_conv0_wgrad: C must be a multiple of 64, B <= 65535");
-    SC_CHECK_ARG(T0 >= 1 && P >= T0 && ld >= (int64_t)(T0 - 1) * C0_S + C0_K, "sc_conv0_wgrad: T0=%d P=%d ld=%lld inconsistent", T0, P, (long long)ld);
+// ------------------------------------------------------------------------------------------------ entries
+// Every operation has one _impl; its uniform and its packed entry forward into it (row_off == nullptr: uniform rows).  row_off: B + 1 device ints in
+// transformer rows (row_off[B] = total_rows); the callers' buffers hold row_scale * total_rows rows at conv layer 0.
+static int conv0_bwd_impl(const char* name, const float* wav, int64_t ld, const float* w, const float* gamma, const float* beta, const void* dy, float* part, int B,
+                          int C, int T0, int P, float eps, void* stream, const int32_t* row_off, int row_scale) {
+    SC_CHECK_ARG(wav && w && gamma && beta && dy && part, "%s: null operand", name);
+    SC_CHECK_ARG(C % 64 == 0 && B <= 65535, "%s: C must be a multiple of 64, B <= 65535", name);
+    SC_CHECK_ARG(T0 >= 1 && (row_off ? row_scale >= 1 : P >= T0) && ld >= (int64_t)(T0 - 1) * C0_S + C0_K, "%s: T0=%d P=%d row_scale=%d ld=%lld inconsistent", name,
+                 T0, P, row_scale, (long long)ld);
     if (B <= 0) return 0;
-    hipLaunchKernelGGL(conv0_wgrad_kernel<false>, dim3(C / 64, B), dim3(256), 0, (hipStream_t)stream, wav, ld, (const bf16_t*)du, part, C, T0, P, nullptr, 0);
+#define C0_LAUNCH(PK_) hipLaunchKernelGGL(conv0_bwd_kernel<PK_>, dim3(C / 64, B), dim3(256), 0, (hipStream_t)stream, wav, ld, w, gamma, beta, (const bf16_t*)dy, part, C, T0, P, eps, row_off, row_scale)
+    if (row_off) C0_LAUNCH(true); else C0_LAUNCH(false);
+#undef C0_LAUNCH
     SC_CHECK_LAUNCH();
     return 0;
 }
 
-extern "C" int sc_posconv_finish_train(const void* x, const int32_t* valid, const void* conv, const float* bias, void* u, void* s, int B, int Tp, int D, int G,
-                                       void* stream) {
-    SC_CHECK_ARG(x && valid && conv && bias && u && s, "sc_posconv_finish_train: null operand");
-    SC_CHECK_ARG(D % G == 0 && (D / G) % 4 == 0, "sc_posconv_finish_train: D/G must be a multiple of 4");
-    const int64_t n4 = (int64_t)B * Tp * D / 4;
-    if (n4 <= 0) return 0;
-    hipLaunchKernelGGL(posconv_finish_train_kernel, dim3((unsigned)((n4 + 255) / 256)), dim3(256), 0, (hipStream_t)stream, (const bf16_t*)x, valid,
-                       (const bf16_t*)conv, bias, (bf16_t*)u, (bf16_t*)s, B, Tp, D, G);
-    SC_CHECK_LAUNCH();
-    return 0;
-}
-
-extern "C" int sc_posconv_dgrad_finish(const void* convT, const void* ds, const int32_t* valid, void* dx, int B, int Tp, int D, int G, void* stream) {
-    SC_CHECK_ARG(convT && ds && valid && dx, "sc_posconv_dgrad_finish: null operand");
-    SC_CHECK_ARG(D % G == 0 && (D / G) % 4 == 0, "sc_posconv_dgrad_finish: D/G must be a multiple of 4");
-    const int64_t n4 = (int64_t)B * Tp * D / 4;
-    if (n4 <= 0) return 0;
-    hipLaunchKernelGGL(posconv_dgrad_finish_kernel, dim3((unsigned)((n4 + 255) / 256)), dim3(256), 0, (hipStream_t)stream, (const bf16_t*)convT, (const bf16_t*)ds,
-                       valid, (bf16_t*)dx, B, Tp, D, G);
-    SC_CHECK_LAUNCH();
-    return 0;
-}
-
-extern "C" int sc_reverse_rows_bf16(const void* in, void* out, int B, int T, int D, void* stream) {
-    SC_CHECK_ARG(in && out && in != out, "sc_reverse_rows_bf16: null operand or in-place");
-    SC_CHECK_ARG(D % 4 == 0, "sc_reverse_rows_bf16: D must be a multiple of 4");
-    const int64_t n4 = (int64_t)B * T * D / 4;
-    if (n4 <= 0) return 0;
-    hipLaunchKernelGGL(reverse_rows_kernel, dim3((unsigned)((n4 + 255) / 256)), dim3(256), 0, (hipStream_t)stream, (const bf16_t*)in, (bf16_t*)out, B, T, D);
+static int conv0_wgrad_impl(const char* name, const float* wav, int64_t ld, const void* du, float* part, int B, int C, int T0, int P, void* stream,
+                            const int32_t* row_off, int row_scale) {
+    SC_CHECK_ARG(wav && du && part, "%s: null operand", name);
+    SC_CHECK_ARG(C % 64 == 0 && B <= 65535, "%s: C must be a multiple of 64, B <= 65535", name);
+    SC_CHECK_ARG(T0 >= 1 && (row_off ? row_scale >= 1 : P >= T0) && ld >= (int64_t)(T0 - 1) * C0_S + C0_K, "%s: T0=%d P=%d row_scale=%d ld=%lld inconsistent", name,
+                 T0, P, row_scale, (long long)ld);
+    if (B <= 0) return 0;
+#define C0_LAUNCH(PK_) hipLaunchKernelGGL(conv0_wgrad_kernel<PK_>, dim3(C / 64, B), dim3(256), 0, (hipStream_t)stream, wav, ld, (const bf16_t*)du, part, C, T0, P, row_off, row_scale)
+    if (row_off) C0_LAUNCH(true); else C0_LAUNCH(false);
+#undef C0_LAUNCH
     SC_CHECK_LAUNCH();
     return 0;
 }
 
 extern "C" int sc_conv0_bwd(const float* wav, int64_t ld, const float* w, const float* gamma, const float* beta, const void* dy, float* part, int B, int C, int T0,
                             int P, float eps, void* stream) {
-    SC_CHECK_ARG(wav && w && gamma && beta && dy && part, "sc_conv0_bwd: null operand");
-    SC_CHECK_ARG(C % 64 == 0 && B <= 65535, "sc_conv0_bwd: C must be a multiple of 64, B <= 65535");
-    SC_CHECK_ARG(T0 >= 1 && P >= T0 && ld >= (int64_t)(T0 - 1) * C0_S + C0_K, "sc_conv0_bwd: T0=%d P=%d ld=%lld inconsistent", T0, P, (long long)ld);
-    if (B <= 0) return 0;
-    hipLaunchKernelGGL(conv0_bwd_kernel<false>, dim3(C / 64, B), dim3(256), 0, (hipStream_t)stream, wav, ld, w, gamma, beta, (const bf16_t*)dy, part, C, T0, P, eps,
-                       nullptr, 0);
-    SC_CHECK_LAUNCH();
-    return 0;
+    return conv0_bwd_impl("sc_conv0_bwd", wav, ld, w, gamma, beta, dy, part, B, C, T0, P, eps, stream, nullptr, 0);
 }
 
-// ------------------------------------------------------------------------------------------------ packed (padding-free) batches
-// row_off: B + 1 device ints in transformer rows (row_off[B] = total_rows); the callers' buffers hold row_scale * total_rows rows at conv layer 0.
 extern "C" int sc_conv0_bwd_packed(const float* wav, int64_t ld, const float* w, const float* gamma, const float* beta, const void* dy, float* part, int B, int C,
                                    int T0, const int32_t* row_off, int row_scale, float eps, void* stream) {
-    SC_CHECK_ARG(wav && w && gamma && beta && dy && part && row_off, "sc_conv0_bwd_packed: null operand");
-    SC_CHECK_ARG(C % 64 == 0 && B <= 65535, "sc_conv0_bwd_packed: C must be a multiple of 64, B <= 65535");
-    SC_CHECK_ARG(T0 >= 1 && row_scale >= 1 && ld >= (int64_t)(T0 - 1) * C0_S + C0_K, "sc_conv0_bwd_packed: T0=%d row_scale=%d ld=%lld inconsistent", T0, row_scale,
-                 (long long)ld);
-    if (B <= 0) return 0;
-    hipLaunchKernelGGL(conv0_bwd_kernel<true>, dim3(C / 64, B), dim3(256), 0, (hipStream_t)stream, wav, ld, w, gamma, beta, (const bf16_t*)dy, part, C, T0, 0, eps,
-                       row_off, row_scale);
-    SC_CHECK_LAUNCH();
-    return 0;
+    SC_CHECK_ARG(row_off, "sc_conv0_bwd_packed: null operand");
+    return conv0_bwd_impl("sc_conv0_bwd_packed", wav, ld, w, gamma, beta, dy, part, B, C, T0, 0, eps, stream, row_off, row_scale);
+}
+
+extern "C" int sc_conv0_wgrad(const float* wav, int64_t ld, const void* du, float* part, int B, int C, int T0, int P, void* stream) {
+    return conv0_wgrad_impl("sc_conv0_wgrad", wav, ld, du, part, B, C, T0, P, stream, nullptr, 0);
 }
 
 extern "C" int sc_conv0_wgrad_packed(const float* wav, int64_t ld, const void* du, float* part, int B, int C, int T0, const int32_t* row_off, int row_scale,
                                      void* stream) {
-    SC_CHECK_ARG(wav && du && part && row_off, "sc_conv0_wgrad_packed: null operand");
-    SC_CHECK_ARG(C % 64 == 0 && B <= 65535, "sc_conv0_wgrad_packed: C must be a multiple of 64, B <= 65535");
-    SC_CHECK_ARG(T0 >= 1 && row_scale >= 1 && ld >= (int64_t)(T0 - 1) * C0_S + C0_K, "sc_conv0_wgrad_packed: T0=%d row_scale=%d ld=%lld inconsistent", T0, row_scale,
-                 (long long)ld);
-    if (B <= 0) return 0;
-    hipLaunchKernelGGL(conv0_wgrad_kernel<true>, dim3(C / 64, B), dim3(256), 0, (hipStream_t)stream, wav, ld, (const bf16_t*)du, part, C, T0, 0, row_off, row_scale);
-    SC_CHECK_LAUNCH();
+    SC_CHECK_ARG(row_off, "sc_conv0_wgrad_packed: null operand");
+    return conv0_wgrad_impl("sc_conv0_wgrad_packed", wav, ld, du, part, B, C, T0, 0, stream, row_off, row_scale);
+}
+
+#define SC_PACKED_ROWS_CHECK(name) \
+    SC_CHECK_ARG(B > 0 && total_rows > 0 && total_rows * D < (int64_t)0x7fffffff * 8, "%s: B=%d total_rows=%lld out of range", name, B, (long long)total_rows)
+
+// The row-streaming kernels' shared checks -> elements per thread (8 or 4), 0 when there is nothing to do, -1 on a bad argument.  The uniform entries accept a
+// group width that is a multiple of 4 and any row count (none: no launch); the packed entries need a multiple of 8, B > 0 and total_rows > 0.
+static int rows_vec(const char* name, int D, int G, const int32_t* row_off, int B, int64_t total_rows) {
+    const int need = row_off ? 8 : 4;
+    SC_CHECK_ARG(G > 0 && D % G == 0 && (D / G) % need == 0, "%s: D/G must be a multiple of %d", name, need);
+    if (row_off) SC_PACKED_ROWS_CHECK(name);
+    else if (total_rows <= 0 || D <= 0) return 0;
+    return (D / G) % 8 == 0 ? 8 : 4;
+}
+#define ROWS_LAUNCH(kernel, v, ...)                                                                                                 \
+    do {                                                                                                                            \
+        const dim3 grid_((unsigned)((rows * D / (v) + 255) / 256));                                                                 \
+        if (row_off) hipLaunchKernelGGL((kernel<8, true>), grid_, dim3(256), 0, (hipStream_t)stream, __VA_ARGS__);                  \
+        else if ((v) == 8) hipLaunchKernelGGL((kernel<8, false>), grid_, dim3(256), 0, (hipStream_t)stream, __VA_ARGS__);           \
+        else hipLaunchKernelGGL((kernel<4, false>), grid_, dim3(256), 0, (hipStream_t)stream, __VA_ARGS__);                         \
+        SC_CHECK_LAUNCH();                                                                                                          \
+    } while (0)
+
+static int posconv_finish_train_impl(const char* name, const void* x, const int32_t* valid, const void* conv, const float* bias, void* u, void* s, int B, int Tp,
+                                     int D, int G, void* stream, const int32_t* row_off, int64_t rows) {
+    SC_CHECK_ARG(x && valid && conv && bias && u && s, "%s: null operand", name);
+    const int v = rows_vec(name, D, G, row_off, B, rows);
+    if (v <= 0) return v;
+    ROWS_LAUNCH(posconv_finish_train_kernel, v, (const bf16_t*)x, valid, (const bf16_t*)conv, bias, (bf16_t*)u, (bf16_t*)s, row_off, B, Tp, rows, D, G);
     return 0;
 }
 
-#define SC_PACKED_ROWS_CHECK(name)                                                                                                             \
-    SC_CHECK_ARG(B > 0 && total_rows > 0 && total_rows * D < (int64_t)0x7fffffff * 8, name ": B=%d total_rows=%lld out of range", B, (long long)total_rows)
+static int posconv_dgrad_finish_impl(const char* name, const void* convT, const void* ds, const int32_t* valid, void* dx, int B, int Tp, int D, int G, void* stream,
+                                     const int32_t* row_off, int64_t rows) {
+    SC_CHECK_ARG(convT && ds && valid && dx, "%s: null operand", name);
+    const int v = rows_vec(name, D, G, row_off, B, rows);
+    if (v <= 0) return v;
+    ROWS_LAUNCH(posconv_dgrad_finish_kernel, v, (const bf16_t*)convT, (const bf16_t*)ds, valid, (bf16_t*)dx, row_off, B, Tp, rows, D, G);
+    return 0;
+}
+
+static int reverse_rows_impl(const char* name, const void* in, void* out, int B, int T, int D, void* stream, const int32_t* row_off, int64_t rows) {
+    SC_CHECK_ARG(in && out && in != out, "%s: null operand or in-place", name);
+    const int v = rows_vec(name, D, 1, row_off, B, rows);
+    if (v <= 0) return v;
+    ROWS_LAUNCH(reverse_rows_kernel, v, (const bf16_t*)in, (bf16_t*)out, row_off, B, T, rows, D);
+    return 0;
+}
+#undef ROWS_LAUNCH
+
+extern "C" int sc_posconv_finish_train(const void* x, const int32_t* valid, const void* conv, const float* bias, void* u, void* s, int B, int Tp, int D, int G,
+                                       void* stream) {
+    return posconv_finish_train_impl("sc_posconv_finish_train", x, valid, conv, bias, u, s, B, Tp, D, G, stream, nullptr, (int64_t)B * Tp);
+}
 
 extern "C" int sc_posconv_finish_train_packed(const void* x, const int32_t* valid, const int32_t* row_off, const void* conv, const float* bias, void* u, void* s,
                                               int B, int64_t total_rows, int D, int G, void* stream) {
-    SC_CHECK_ARG(x && valid && row_off && conv && bias && u && s, "sc_posconv_finish_train_packed: null operand");
-    SC_CHECK_ARG(G > 0 && D % G == 0 && (D / G) % 8 == 0, "sc_posconv_finish_train_packed: D/G must be a multiple of 8");
-    SC_PACKED_ROWS_CHECK("sc_posconv_finish_train_packed");
-    const int64_t n8 = total_rows * D / 8;
-    hipLaunchKernelGGL(posconv_finish_train_packed_kernel, dim3((unsigned)((n8 + 255) / 256)), dim3(256), 0, (hipStream_t)stream, (const bf16_t*)x, valid, row_off,
-                       (const bf16_t*)conv, bias, (bf16_t*)u, (bf16_t*)s, B, total_rows, D, G);
-    SC_CHECK_LAUNCH();
-    return 0;
+    SC_CHECK_ARG(row_off, "sc_posconv_finish_train_packed: null operand");
+    return posconv_finish_train_impl("sc_posconv_finish_train_packed", x, valid, conv, bias, u, s, B, 0, D, G, stream, row_off, total_rows);
+}
+
+extern "C" int sc_posconv_dgrad_finish(const void* convT, const void* ds, const int32_t* valid, void* dx, int B, int Tp, int D, int G, void* stream) {
+    return posconv_dgrad_finish_impl("sc_posconv_dgrad_finish", convT, ds, valid, dx, B, Tp, D, G, stream, nullptr, (int64_t)B * Tp);
 }
 
 extern "C" int sc_posconv_dgrad_finish_packed(const void* convT, const void* ds, const int32_t* valid, const int32_t* row_off, void* dx, int B, int64_t total_rows,
                                               int D, int G, void* stream) {
-    SC_CHECK_ARG(convT && ds && valid && row_off && dx, "sc_posconv_dgrad_finish_packed: null operand");
-    SC_CHECK_ARG(G > 0 && D % G == 0 && (D / G) % 8 == 0, "sc_posconv_dgrad_finish_packed: D/G must be a multiple of 8");
-    SC_PACKED_ROWS_CHECK("sc_posconv_dgrad_finish_packed");
-    const int64_t n8 = total_rows * D / 8;
-    hipLaunchKernelGGL(posconv_dgrad_finish_packed_kernel, dim3((unsigned)((n8 + 255) / 256)), dim3(256), 0, (hipStream_t)stream, (const bf16_t*)convT,
-                       (const bf16_t*)ds, valid, row_off, (bf16_t*)dx, B, total_rows, D, G);
-    SC_CHECK_LAUNCH();
-    return 0;
+    SC_CHECK_ARG(row_off, "sc_posconv_dgrad_finish_packed: null operand");
+    return posconv_dgrad_finish_impl("sc_posconv_dgrad_finish_packed", convT, ds, valid, dx, B, 0, D, G, stream, row_off, total_rows);
+}
+
+extern "C" int sc_reverse_rows_bf16(const void* in, void* out, int B, int T, int D, void* stream) {
+    return reverse_rows_impl("sc_reverse_rows_bf16", in, out, B, T, D, stream, nullptr, (int64_t)B * T);
 }
 
 extern "C" int sc_reverse_rows_packed_bf16(const void* in, const int32_t* row_off, void* out, int B, int64_t total_rows, int D, void* stream) {
-    SC_CHECK_ARG(in && out && row_off && in != out, "sc_reverse_rows_packed_bf16: null operand or in-place");
-    SC_CHECK_ARG(D % 8 == 0, "sc_reverse_rows_packed_bf16: D must be a multiple of 8");
-    SC_PACKED_ROWS_CHECK("sc_reverse_rows_packed_bf16");
-    const int64_t n8 = total_rows * D / 8;
-    hipLaunchKernelGGL(reverse_rows_packed_kernel, dim3((unsigned)((n8 + 255) / 256)), dim3(256), 0, (hipStream_t)stream, (const bf16_t*)in, row_off, (bf16_t*)out,
-                       B, total_rows, D);
-    SC_CHECK_LAUNCH();
-    return 0;
+    SC_CHECK_ARG(row_off, "sc_reverse_rows_packed_bf16: null operand");
+    return reverse_rows_impl("sc_reverse_rows_packed_bf16", in, out, B, 0, D, stream, row_off, total_rows);
 }
 
 // out bf16 [G][slab_rows][D/G]: row lead + row_off[b] + b * gap + t of group g = row row_off[b] + t of x (columns of group g) for t < min(lim[b], rows_b), zeros

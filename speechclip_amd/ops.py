@@ -461,7 +461,7 @@ def posconv_packed(x, valid_i32, row_off_i32, wg, bias, gamma, beta, B, rows_max
     conv = torch.empty(total_rows * D, device=x.device, dtype=bf16)
     rc = lib().sc_posconv_conv_packed(ptr(x), ptr(valid_i32), ptr(row_off_i32), ptr(wg), ptr(conv), B, rows_max, D, G, Kw, stream())
     if rc == 1:
-        raise SpeechClipHipError(f"packed batches need the windowed positional-conv kernel (D/G in 32/48/64), got D/G = {cg}")
+        raise _lib.SpeechClipHipError(f"packed batches need the windowed positional-conv kernel (D/G in 32/48/64), got D/G = {cg}")
     check(rc, "sc_posconv_conv_packed")
     if out is None:
         out = torch.empty(total_rows, D, device=x.device, dtype=torch.float32 if out_f32 else bf16)
@@ -1062,52 +1062,97 @@ def posconv_pack(x, valid_i32, B, Tp, D, G, Kw):
     return xg
 
 
-def posconv_finish_train(x, valid_i32, conv, bias, B, Tp, D, G):
-    """-> (u, s) bf16 [B*Tp, D]: u = conv + bias regrouped, s = mask(x) + gelu(u)."""
-    u = torch.empty(B * Tp, D, device=x.device, dtype=bf16)
+# The per-utterance kernels serve both layouts: uniform rows (B utterances of Tp rows each) are the packed layout with row_off[b] = b * Tp.  row_off_i32 (B + 1
+# device ints, utterance b owns rows [row_off[b], row_off[b + 1]) of every transformer-level tensor) selects the *_packed entry; the row count is the tensor's own.
+def _rows_of(t, B, Tp, D, row_off_i32):
+    """Row count of the bf16 [rows, D] tensor t: B * Tp on uniform rows, row_off[B] (= what t holds) on packed rows."""
+    assert t.dtype == bf16 and t.is_contiguous() and t.dim() == 2 and t.shape[1] == D
+    assert t.shape[0] == B * Tp if row_off_i32 is None else (row_off_i32.is_cuda and row_off_i32.dtype == torch.int32 and row_off_i32.numel() == B + 1)
+    return t.shape[0]
+
+
+def posconv_finish_train(x, valid_i32, conv, bias, B, Tp, D, G, row_off_i32=None):
+    """-> (u, s) bf16 [rows, D]: u = conv + bias regrouped from the slabs (utterance b = [G][rows_b][D/G] at element row_off[b] * D), s = mask(x) + gelu(u)."""
+    rows = _rows_of(x, B, Tp, D, row_off_i32)
+    assert conv.numel() >= rows * D and bias.numel() == D
+    u = torch.empty(rows, D, device=x.device, dtype=bf16)
     s = torch.empty_like(u)
-    check(lib().sc_posconv_finish_train(ptr(x), ptr(valid_i32), ptr(conv), ptr(bias), ptr(u), ptr(s), B, Tp, D, G, stream()), "sc_posconv_finish_train")
+    if row_off_i32 is None:
+        check(lib().sc_posconv_finish_train(ptr(x), ptr(valid_i32), ptr(conv), ptr(bias), ptr(u), ptr(s), B, Tp, D, G, stream()), "sc_posconv_finish_train")
+    else:
+        check(lib().sc_posconv_finish_train_packed(ptr(x), ptr(valid_i32), ptr(row_off_i32), ptr(conv), ptr(bias), ptr(u), ptr(s), B, rows, D, G, stream()),
+              "sc_posconv_finish_train_packed")
     return u, s
 
 
-def posconv_dgrad_finish(convT, ds, valid_i32, B, Tp, D, G):
-    dx = torch.empty(B * Tp, D, device=ds.device, dtype=bf16)
-    assert ds.dtype == bf16 and ds.is_contiguous()
-    check(lib().sc_posconv_dgrad_finish(ptr(convT), ptr(ds), ptr(valid_i32), ptr(dx), B, Tp, D, G, stream()), "sc_posconv_dgrad_finish")
+def posconv_dgrad_finish(convT, ds, valid_i32, B, Tp, D, G, row_off_i32=None):
+    """dx bf16 [rows, D] = mask(ds + convT regrouped, time reversed inside each utterance's own rows)."""
+    rows = _rows_of(ds, B, Tp, D, row_off_i32)
+    assert convT.numel() >= rows * D
+    dx = torch.empty(rows, D, device=ds.device, dtype=bf16)
+    if row_off_i32 is None:
+        check(lib().sc_posconv_dgrad_finish(ptr(convT), ptr(ds), ptr(valid_i32), ptr(dx), B, Tp, D, G, stream()), "sc_posconv_dgrad_finish")
+    else:
+        check(lib().sc_posconv_dgrad_finish_packed(ptr(convT), ptr(ds), ptr(valid_i32), ptr(row_off_i32), ptr(dx), B, rows, D, G, stream()),
+              "sc_posconv_dgrad_finish_packed")
     return dx
 
 
-def reverse_rows_bf16(x, B, T, D):
-    assert x.dtype == bf16 and x.is_contiguous() and x.numel() == B * T * D
+def reverse_rows_bf16(x, B, T, D, row_off_i32=None):
+    """out[row_off[b] + rows_b - 1 - t] = x[row_off[b] + t]: time reversal inside every utterance's own rows (uniform: out[b, T - 1 - t] = x[b, t])."""
+    rows = _rows_of(x, B, T, D, row_off_i32)
     out = torch.empty_like(x)
-    check(lib().sc_reverse_rows_bf16(ptr(x), ptr(out), B, T, D, stream()), "sc_reverse_rows_bf16")
+    if row_off_i32 is None:
+        check(lib().sc_reverse_rows_bf16(ptr(x), ptr(out), B, T, D, stream()), "sc_reverse_rows_bf16")
+    else:
+        check(lib().sc_reverse_rows_packed_bf16(ptr(x), ptr(row_off_i32), ptr(out), B, rows, D, stream()), "sc_reverse_rows_packed_bf16")
     return out
 
 
-def conv0_bwd(wav, w, gamma, beta, dy, T0, P, eps=1e-5):
-    """wav f32 [B, L]; w f32 [C, 10]; dy bf16 [B*P (+ slack), C] -> (dw f32 [C, 10], dgamma f32 [C], dbeta f32 [C])."""
+def _conv0_grad_rows(wav, dy, C, P, row_off_i32, row_scale):
+    """Checks shared by conv0_bwd / conv0_wgrad.  dy bf16 [rows (+ slack), C]: utterance b's frames at rows b * P .. (uniform, B * P rows) or
+    row_scale * row_off[b] .. (packed, P = row_scale * total_rows rows in all) -> (B, L, partials buffer f32 [B, C * 12])."""
     _need_cuda(wav, dy)
     B, L = wav.shape
+    assert wav.dtype == torch.float32 and wav.is_contiguous() and dy.dtype == bf16 and dy.is_contiguous() and dy.dim() == 2 and dy.shape[1] == C
+    assert dy.shape[0] >= B * P if row_off_i32 is None else (dy.shape[0] >= P and row_off_i32.is_cuda and row_off_i32.dtype == torch.int32 and row_off_i32.numel() == B + 1)
+    return B, L, torch.empty(B, C * 12, device=wav.device, dtype=torch.float32)
+
+
+def conv0_bwd(wav, w, gamma, beta, dy, T0, P, eps=1e-5, row_off_i32=None, row_scale=None):
+    """wav f32 [B, L]; w f32 [C, 10]; dy as _conv0_grad_rows -> (dw f32 [C, 10], dgamma f32 [C], dbeta f32 [C], per-utterance partials f32 [B, C, 12])."""
     C = w.shape[0]
-    assert wav.dtype == torch.float32 and wav.is_contiguous() and w.dtype == torch.float32 and w.is_contiguous() and dy.dtype == bf16 and dy.is_contiguous()
-    part = torch.empty(B, C * 12, device=wav.device, dtype=torch.float32)
-    check(lib().sc_conv0_bwd(ptr(wav), L, ptr(w), ptr(gamma), ptr(beta), ptr(dy), ptr(part), B, C, T0, P, eps, stream()), "sc_conv0_bwd")
+    B, L, part = _conv0_grad_rows(wav, dy, C, P, row_off_i32, row_scale)
+    assert w.dtype == torch.float32 and w.is_contiguous()
+    if row_off_i32 is None:
+        check(lib().sc_conv0_bwd(ptr(wav), L, ptr(w), ptr(gamma), ptr(beta), ptr(dy), ptr(part), B, C, T0, P, eps, stream()), "sc_conv0_bwd")
+    else:
+        check(lib().sc_conv0_bwd_packed(ptr(wav), L, ptr(w), ptr(gamma), ptr(beta), ptr(dy), ptr(part), B, C, T0, ptr(row_off_i32), row_scale, eps, stream()),
+              "sc_conv0_bwd_packed")
     tot = colsum(part).view(C, 12)
-    return tot[:, :10].contiguous(), tot[:, 10].contiguous(), tot[:, 11].contiguous()
+    return tot[:, :10].contiguous(), tot[:, 10].contiguous(), tot[:, 11].contiguous(), part.view(B, C, 12)
 
 
-def conv0_wgrad(wav, du, C, T0, P):
-    """wav f32 [B, L]; du bf16 [B*P (+ slack), C] = gradient of conv layer 0's (pre-norm) output -> (dw f32 [C, 10], dbias f32 [C])."""
-    _need_cuda(wav, du)
-    B, L = wav.shape
-    assert wav.dtype == torch.float32 and wav.is_contiguous() and du.dtype == bf16 and du.is_contiguous()
-    part = torch.empty(B, C * 12, device=wav.device, dtype=torch.float32)
-    check(lib().sc_conv0_wgrad(ptr(wav), L, ptr(du), ptr(part), B, C, T0, P, stream()), "sc_conv0_wgrad")
+def conv0_wgrad(wav, du, C, T0, P, row_off_i32=None, row_scale=None):
+    """wav f32 [B, L]; du (as _conv0_grad_rows) = gradient of conv layer 0's (pre-norm) output -> (dw f32 [C, 10], dbias f32 [C], partials f32 [B, C, 12])."""
+    B, L, part = _conv0_grad_rows(wav, du, C, P, row_off_i32, row_scale)
+    if row_off_i32 is None:
+        check(lib().sc_conv0_wgrad(ptr(wav), L, ptr(du), ptr(part), B, C, T0, P, stream()), "sc_conv0_wgrad")
+    else:
+        check(lib().sc_conv0_wgrad_packed(ptr(wav), L, ptr(du), ptr(part), B, C, T0, ptr(row_off_i32), row_scale, stream()), "sc_conv0_wgrad_packed")
     tot = colsum(part).view(C, 12)
-    return tot[:, :10].contiguous(), tot[:, 10].contiguous()
+    return tot[:, :10].contiguous(), tot[:, 10].contiguous(), part.view(B, C, 12)
 
 
-# ---- the same on packed rows (padding-free whole-encoder training): utterance b owns rows [row_off[b], row_off[b + 1]) of every transformer-level tensor
+# The packed forms under their earlier names (argument order of the C entries): forwards into the merged wrappers above, nothing else.
+posconv_finish_train_packed = lambda x, valid, off, conv, bias, B, total, D, G: posconv_finish_train(x, valid, conv, bias, B, 0, D, G, off)      # noqa: E731
+posconv_dgrad_finish_packed = lambda convT, ds, valid, off, B, total, D, G: posconv_dgrad_finish(convT, ds, valid, B, 0, D, G, off)                 # noqa: E731
+reverse_rows_packed_bf16 = lambda x, off, B, total, D: reverse_rows_bf16(x, B, 0, D, off)                                                             # noqa: E731
+conv0_bwd_packed = lambda wav, w, gamma, beta, dy, T0, off, scale, total, eps=1e-5: conv0_bwd(wav, w, gamma, beta, dy, T0, scale * total, eps, off, scale)      # noqa: E731
+conv0_wgrad_packed = lambda wav, du, C, T0, off, scale, total: conv0_wgrad(wav, du, C, T0, scale * total, off, scale)                                  # noqa: E731
+
+
+# ---- packed rows only (padding-free whole-encoder training)
 def posconv_conv_packed(x, lim_i32, row_off_i32, wg, B, rows_max, total_rows, D, G, Kw):
     """posconv_conv over packed rows: x bf16 [total_rows, D] (rows t >= lim[b] of utterance b read as zero) -> conv slabs, utterance b = [G][rows_b][D/G] at
     element row_off[b] * D."""
@@ -1116,35 +1161,9 @@ def posconv_conv_packed(x, lim_i32, row_off_i32, wg, B, rows_max, total_rows, D,
     conv = torch.empty(total_rows * D, device=x.device, dtype=bf16)
     rc = lib().sc_posconv_conv_packed(ptr(x), ptr(lim_i32), ptr(row_off_i32), ptr(wg), ptr(conv), B, rows_max, D, G, Kw, stream())
     if rc == 1:
-        raise SpeechClipHipError(f"packed batches need the windowed positional-conv kernel (D/G in 32/48/64), got D/G = {D // G}")
+        raise _lib.SpeechClipHipError(f"packed batches need the windowed positional-conv kernel (D/G in 32/48/64), got D/G = {D // G}")
     check(rc, "sc_posconv_conv_packed")
     return conv
-
-
-def posconv_finish_train_packed(x, valid_i32, row_off_i32, conv, bias, B, total_rows, D, G):
-    """posconv_finish_train over packed rows -> (u, s) bf16 [total_rows, D]."""
-    assert x.dtype == bf16 and x.is_contiguous() and x.shape == (total_rows, D) and conv.numel() >= total_rows * D and bias.numel() == D
-    u = torch.empty(total_rows, D, device=x.device, dtype=bf16)
-    s = torch.empty_like(u)
-    check(lib().sc_posconv_finish_train_packed(ptr(x), ptr(valid_i32), ptr(row_off_i32), ptr(conv), ptr(bias), ptr(u), ptr(s), B, total_rows, D, G, stream()),
-          "sc_posconv_finish_train_packed")
-    return u, s
-
-
-def posconv_dgrad_finish_packed(convT, ds, valid_i32, row_off_i32, B, total_rows, D, G):
-    assert ds.dtype == bf16 and ds.is_contiguous() and ds.shape == (total_rows, D) and convT.numel() >= total_rows * D
-    dx = torch.empty(total_rows, D, device=ds.device, dtype=bf16)
-    check(lib().sc_posconv_dgrad_finish_packed(ptr(convT), ptr(ds), ptr(valid_i32), ptr(row_off_i32), ptr(dx), B, total_rows, D, G, stream()),
-          "sc_posconv_dgrad_finish_packed")
-    return dx
-
-
-def reverse_rows_packed_bf16(x, row_off_i32, B, total_rows, D):
-    """out[row_off[b] + rows_b - 1 - t] = x[row_off[b] + t]: time reversal inside every utterance's own rows."""
-    assert x.dtype == bf16 and x.is_contiguous() and x.shape == (total_rows, D)
-    out = torch.empty_like(x)
-    check(lib().sc_reverse_rows_packed_bf16(ptr(x), ptr(row_off_i32), ptr(out), B, total_rows, D, stream()), "sc_reverse_rows_packed_bf16")
-    return out
 
 
 def posconv_pack_gapped(x, lim_i32, row_off_i32, B, total_rows, D, G, gap, lead, slab_rows):
@@ -1155,33 +1174,6 @@ def posconv_pack_gapped(x, lim_i32, row_off_i32, B, total_rows, D, G, gap, lead,
     check(lib().sc_posconv_pack_gapped(ptr(x), ptr(lim_i32), ptr(row_off_i32), ptr(out), B, total_rows, D, G, gap, lead, slab_rows, stream()),
           "sc_posconv_pack_gapped")
     return out
-
-
-def conv0_bwd_packed(wav, w, gamma, beta, dy, T0, row_off_i32, row_scale, total_rows, eps=1e-5):
-    """conv0_bwd with dy bf16 [row_scale * total_rows (+ slack), C] on packed rows (utterance b's frames at rows row_scale * row_off[b] ..) -> (dw, dgamma, dbeta);
-    also returns the per-utterance partials f32 [B, C, 12]."""
-    _need_cuda(wav, dy, row_off_i32)
-    B, L = wav.shape
-    C = w.shape[0]
-    assert wav.dtype == torch.float32 and wav.is_contiguous() and w.dtype == torch.float32 and w.is_contiguous() and dy.dtype == bf16 and dy.is_contiguous()
-    assert dy.shape[0] >= row_scale * total_rows and dy.shape[1] == C and row_off_i32.dtype == torch.int32 and row_off_i32.numel() == B + 1
-    part = torch.empty(B, C * 12, device=wav.device, dtype=torch.float32)
-    check(lib().sc_conv0_bwd_packed(ptr(wav), L, ptr(w), ptr(gamma), ptr(beta), ptr(dy), ptr(part), B, C, T0, ptr(row_off_i32), row_scale, eps, stream()),
-          "sc_conv0_bwd_packed")
-    tot = colsum(part).view(C, 12)
-    return tot[:, :10].contiguous(), tot[:, 10].contiguous(), tot[:, 11].contiguous(), part.view(B, C, 12)
-
-
-def conv0_wgrad_packed(wav, du, C, T0, row_off_i32, row_scale, total_rows):
-    """conv0_wgrad with du bf16 [row_scale * total_rows (+ slack), C] on packed rows -> (dw f32 [C, 10], dbias f32 [C], per-utterance partials f32 [B, C, 12])."""
-    _need_cuda(wav, du, row_off_i32)
-    B, L = wav.shape
-    assert wav.dtype == torch.float32 and wav.is_contiguous() and du.dtype == bf16 and du.is_contiguous()
-    assert du.shape[0] >= row_scale * total_rows and du.shape[1] == C and row_off_i32.dtype == torch.int32 and row_off_i32.numel() == B + 1
-    part = torch.empty(B, C * 12, device=wav.device, dtype=torch.float32)
-    check(lib().sc_conv0_wgrad_packed(ptr(wav), L, ptr(du), ptr(part), B, C, T0, ptr(row_off_i32), row_scale, stream()), "sc_conv0_wgrad_packed")
-    tot = colsum(part).view(C, 12)
-    return tot[:, :10].contiguous(), tot[:, 10].contiguous(), part.view(B, C, 12)
 
 
 def gemm_batched2(a, lda, stride_a, stride_a2, w, ldw, stride_w, stride_w2, out, ldc, stride_c, stride_c2, M, N, K, outer, inner):

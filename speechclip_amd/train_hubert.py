@@ -105,12 +105,14 @@ def attention_bwd_packed(qkv: torch.Tensor, att: torch.Tensor, datt: torch.Tenso
 
 
 def _pack_of(meta, dev):
-    """(row_off device ints, rows_max) of a packed batch (meta["pack"]), or None for the padded layout."""
+    """(row_off device ints, rows_max, total, scale0) of a packed batch (meta["pack"]: the one place that reads it), or None for the padded layout.
+    scale0 = conv-layer-0 rows per transformer row: only the front-end node (train_front.py) needs it, 0 where the batch does not carry it."""
     pk = meta.get("pack")
     if pk is None:
         return None
     off = pk["row_off"]
-    return (off if torch.is_tensor(off) else ops.dev_ints(off, torch.int32, dev)), int(pk["rows_max"])
+    off = off if torch.is_tensor(off) else ops.dev_ints(off, torch.int32, dev)
+    return off, int(pk["rows_max"]), int(pk["total"]), int(pk.get("scale0", 0))
 
 
 def _qkv_rows(pk, M, Lp, Tp, d, dev):
@@ -163,7 +165,7 @@ class HubertLayersTrainFn(torch.autograd.Function):
         M, d = h_in.shape
         dev = h_in.device
         pk = _pack_of(meta, dev)         # packed rows: M = sum_b rows_b, Tp = the longest utterance's rows
-        assert (M == B * Tp if pk is None else M == meta["pack"]["total"]) and d == H * 64
+        assert M == (B * Tp if pk is None else pk[2]) and d == H * 64
         Lp = -(-Tp // 64) * 64
         pre_ln = bool(meta.get("pre_ln", False))
         if pre_ln:

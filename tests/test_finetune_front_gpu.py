@@ -40,8 +40,8 @@ def test_conv0_backward_vs_autograd(B, C, L):
     y.backward(dy.float().permute(0, 2, 1))
     dyp = torch.zeros(B, P, C, dtype=BF)
     dyp[:, :T0] = dy
-    dw, dg, db = ops.conv0_bwd(wav.cuda(), w.detach().reshape(C, 10).cuda().contiguous(), gamma.detach().cuda(), beta.detach().cuda(),
-                               dyp.view(B * P, C).cuda(), T0, P)
+    dw, dg, db, _ = ops.conv0_bwd(wav.cuda(), w.detach().reshape(C, 10).cuda().contiguous(), gamma.detach().cuda(), beta.detach().cuda(),
+                                  dyp.view(B * P, C).cuda(), T0, P)
     _close("dw", dw, w.grad.view(C, 10), 0.999, 0.02)
     _close("dgamma", dg, gamma.grad, 0.999, 0.02)
     _close("dbeta", db, beta.grad, 0.999, 0.02)

@@ -1,5 +1,5 @@
 """Kernel-level tests of the packed (padding-free) front-end BACKWARD entry points (csrc/train_front.hip), through the C ABI / `ops`:
-sc_posconv_finish_train_packed, sc_reverse_rows_packed_bf16, sc_posconv_dgrad_finish_packed, sc_posconv_pack_gapped (bitwise against their padded twins on
+sc_posconv_finish_train_packed, sc_reverse_rows_packed_bf16, sc_posconv_dgrad_finish_packed, sc_posconv_pack_gapped (bitwise against the uniform entries on
 every utterance's own rows, exact zeros where the contract says zero, every row written: the outputs are poisoned first), sc_conv0_bwd_packed /
 sc_conv0_wgrad_packed (fp64 restatement per utterance on its own zero-padded wave, at the tolerance the padded twins are tested at) and the packed
 positional-conv weight gradient against the padded one.
@@ -95,7 +95,7 @@ def test_elementwise_packed_kernels_match_their_padded_twins_bitwise(D, G):
     u1, s1 = _nan(total, D), _nan(total, D)
     check(lib().sc_posconv_finish_train_packed(ptr(xp), ptr(valid_d), ptr(off_d), ptr(slab), ptr(bias), ptr(u1), ptr(s1), B, total, D, G, stream()), "finish_train_packed")
     assert torch.equal(u1, _pack_rows(u0.view(B, Tp, D), rows)) and torch.equal(s1, _pack_rows(s0.view(B, Tp, D), rows))
-    wu, ws_ = ops.posconv_finish_train_packed(xp, valid_d, off_d, slab, bias, B, total, D, G)
+    wu, ws_ = ops.posconv_finish_train(xp, valid_d, slab, bias, B, Tp, D, G, row_off_i32=off_d)
     assert torch.equal(wu, u1) and torch.equal(ws_, s1)
     # ---- reverse: inside each utterance's own rows
     r1 = _nan(total, D)
@@ -103,7 +103,7 @@ def test_elementwise_packed_kernels_match_their_padded_twins_bitwise(D, G):
     assert torch.equal(r1, torch.cat([x[b, :r].flip(0) for b, r in enumerate(rows)], 0))
     for b, r in enumerate(rows):      # the padded twin on an utterance of exactly rows_b frames
         assert torch.equal(r1[off[b]:off[b + 1]], ops.reverse_rows_bf16(x[b, :r].contiguous(), 1, r, D))
-    assert torch.equal(ops.reverse_rows_packed_bf16(xp, off_d, B, total, D), r1)
+    assert torch.equal(ops.reverse_rows_bf16(xp, B, Tp, D, row_off_i32=off_d), r1)
     # ---- dgrad-finish: packed slab row rows_b - 1 - t <-> padded slab row Tp - 1 - t
     dx0 = ops.posconv_dgrad_finish(conv.view(-1), ds.view(B * Tp, D), valid_d, B, Tp, D, G).view(B, Tp, D)
     slabT = torch.cat([conv[b, :, Tp - r:].reshape(-1) for b, r in enumerate(rows)]).contiguous()
@@ -112,7 +112,7 @@ def test_elementwise_packed_kernels_match_their_padded_twins_bitwise(D, G):
     assert torch.equal(dx1, _pack_rows(dx0, rows))
     for b in range(B):                # exactly zero from valid_b on (the positional conv's input mask), non-zero below
         assert bool((dx1[off[b] + valid[b]:off[b + 1]] == 0).all()) and bool((dx1[off[b]:off[b] + valid[b]] != 0).any())
-    assert torch.equal(ops.posconv_dgrad_finish_packed(slabT, dsp, valid_d, off_d, B, total, D, G), dx1)
+    assert torch.equal(ops.posconv_dgrad_finish(slabT, dsp, valid_d, B, Tp, D, G, row_off_i32=off_d), dx1)
     # ---- window pack: Kw zero rows between utterances; the padded twin's rows Kw/2 + t of utterance b at gapped row Kw/2 + row_off[b] + b Kw + t
     xg0 = ops.posconv_pack(x.view(B * Tp, D), valid_d, B, Tp, D, G, KW)[:B * G * (Tp + KW) * cg].view(B, G, Tp + KW, cg)
     slab_rows = KW // 2 + total + B * KW + 37             # more rows than the minimum: the tail must be written (zeros) too
@@ -177,7 +177,8 @@ def test_conv0_bwd_packed_vs_fp64_per_utterance(rows_list):
     w = 0.3 * torch.randn(C, 1, 10, generator=g)
     gamma, beta = 1 + 0.2 * torch.randn(C, generator=g), 0.1 * torch.randn(C, generator=g)
     dy = _packed_dy(rows, T0, C, g)
-    dw, dg, db, part = ops.conv0_bwd_packed(wav.cuda(), w.reshape(C, 10).cuda().contiguous(), gamma.cuda(), beta.cuda(), dy.cuda(), T0, _dev(off), 64, off[-1])
+    dw, dg, db, part = ops.conv0_bwd(wav.cuda(), w.reshape(C, 10).cuda().contiguous(), gamma.cuda(), beta.cuda(), dy.cuda(), T0, 64 * off[-1],
+                                      row_off_i32=_dev(off), row_scale=64)
     part = part.cpu()
     tot = torch.zeros(C, 12, dtype=torch.float64)
     for b in range(B):
@@ -212,7 +213,7 @@ def test_conv0_wgrad_packed_vs_fp64_per_utterance(rows_list):
     g = _g(23)
     wav = _waves(B, g)
     du = _packed_dy(rows, T0, C, g)
-    dw, dbias, part = ops.conv0_wgrad_packed(wav.cuda(), du.cuda(), C, T0, _dev(off), 64, off[-1])
+    dw, dbias, part = ops.conv0_wgrad(wav.cuda(), du.cuda(), C, T0, 64 * off[-1], row_off_i32=_dev(off), row_scale=64)
     part = part.cpu().double()
     for b in range(B):
         n = min(T0, 64 * rows[b])
@@ -258,3 +259,99 @@ def test_packed_posconv_weight_gradient_matches_the_padded_one(D, G):
     F.conv1d(xm.permute(0, 2, 1), w, padding=KW // 2, groups=G)[:, :, :-1].backward(du.double().permute(0, 2, 1))
     _close("packed vs padded", dw1, dw0, 0.98, 0.1)
     _close("packed vs fp64", dw1, w.grad, 0.98, 0.1)
+
+
+# ---------------------------------------------------------------------------------------------------------------- one kernel per operation
+def _slab(B, G, Tp, cg, g):
+    return torch.randn(B, G, Tp, cg, generator=g).to(BF).cuda()
+
+
+@pytest.mark.parametrize("D,G", [(128, 4), (768, 16)])
+def test_uniform_offsets_through_the_packed_entries_equal_the_uniform_entries_bitwise(D, G):
+    """The padded layout is the packed one with row_off[b] = b * Tp: the *_packed entries on row_off = [0, 7, 14, 21] against the uniform entries on B = 3, Tp = 7
+    (valid = [7, 3, 0]; D/G = 32 and 48, the second no power of two and straddling the 8-wide chunks), outputs poisoned first."""
+    from speechclip_amd import ops
+    from speechclip_amd._lib import check, lib, ptr, stream
+    B, Tp, valid, off = 3, 7, [7, 3, 0], [0, 7, 14, 21]
+    cg, total = D // G, B * Tp
+    g = _g(D + 7)
+    x = torch.randn(total, D, generator=g).to(BF).cuda()
+    ds = torch.randn(total, D, generator=g).to(BF).cuda()
+    conv = _slab(B, G, Tp, cg, g).view(-1)
+    bias = torch.randn(D, generator=g).cuda()
+    valid_d, off_d = _dev(valid), _dev(off)
+    u0, s0 = ops.posconv_finish_train(x, valid_d, conv, bias, B, Tp, D, G)
+    u1, s1 = _nan(total, D), _nan(total, D)
+    check(lib().sc_posconv_finish_train_packed(ptr(x), ptr(valid_d), ptr(off_d), ptr(conv), ptr(bias), ptr(u1), ptr(s1), B, total, D, G, stream()), "finish_train_packed")
+    assert torch.equal(u1, u0) and torch.equal(s1, s0)
+    r1 = _nan(total, D)
+    check(lib().sc_reverse_rows_packed_bf16(ptr(x), ptr(off_d), ptr(r1), B, total, D, stream()), "reverse_rows_packed")
+    assert torch.equal(r1, ops.reverse_rows_bf16(x, B, Tp, D)) and torch.equal(r1.view(B, Tp, D), x.view(B, Tp, D).flip(1))
+    dx1 = _nan(total, D)
+    check(lib().sc_posconv_dgrad_finish_packed(ptr(conv), ptr(ds), ptr(valid_d), ptr(off_d), ptr(dx1), B, total, D, G, stream()), "dgrad_finish_packed")
+    assert torch.equal(dx1, ops.posconv_dgrad_finish(conv, ds, valid_d, B, Tp, D, G))
+    for b, v in enumerate(valid):
+        assert bool((dx1.view(B, Tp, D)[b, v:] == 0).all()) and (v == 0 or bool((dx1.view(B, Tp, D)[b, :v] != 0).any()))
+
+
+def test_uniform_offsets_through_the_packed_conv0_entries_equal_the_uniform_entries_bitwise():
+    """sc_conv0_bwd_packed / sc_conv0_wgrad_packed with row_off = [0, 2, 4], row_scale = 64 (P = 128 rows per utterance) against sc_conv0_bwd / sc_conv0_wgrad
+    with P = 128: B = 2, C = 64, L = 330 (T0 = 65 frames <= 128, so the packed frame limit min(T0, 64 * 2) is T0)."""
+    from speechclip_amd import ops
+    B, C, L, Tp, scale, P = 2, 64, 330, 2, 64, 128
+    T0 = (L - 10) // 5 + 1
+    assert T0 == 65 and scale * Tp == P
+    g = _g(330)
+    wav = (0.3 * torch.randn(B, L, generator=g) + 0.05).cuda()
+    w = (0.3 * torch.randn(C, 10, generator=g)).cuda()
+    gamma, beta = (1 + 0.2 * torch.randn(C, generator=g)).cuda(), (0.1 * torch.randn(C, generator=g)).cuda()
+    dy = torch.randn(B * P + 8, C, generator=g).to(BF).cuda()
+    off_d = _dev([0, Tp, 2 * Tp])
+    uni = ops.conv0_bwd(wav, w, gamma, beta, dy, T0, P)
+    pkd = ops.conv0_bwd(wav, w, gamma, beta, dy, T0, B * P, row_off_i32=off_d, row_scale=scale)
+    for name, a, b in zip(("dw", "dgamma", "dbeta", "partials"), uni, pkd):
+        assert torch.equal(a, b), name
+    uni = ops.conv0_wgrad(wav, dy, C, T0, P)
+    pkd = ops.conv0_wgrad(wav, dy, C, T0, B * P, row_off_i32=off_d, row_scale=scale)
+    for name, a, b in zip(("dw", "dbias", "partials"), uni, pkd):
+        assert torch.equal(a, b), name
+
+
+def test_four_wide_instantiation_of_the_row_kernels():
+    """D/G = 20 is a multiple of 4 but not of 8: the uniform entries run the 4-elements-per-thread instantiation.  reverse and dgrad-finish are exact (a copy; one
+    fp32 add and one RNE rounding on both sides), finish-train is held to the bounds of tests/test_untested_entries_gpu.py::test_posconv_finish_train_both_outputs."""
+    from speechclip_amd import ops
+    D, G, B, Tp, valid = 80, 4, 2, 5, [5, 2]
+    cg = D // G
+    g = _g(80)
+    x = torch.randn(B, Tp, D, generator=g).to(BF)
+    ds = torch.randn(B, Tp, D, generator=g).to(BF)
+    conv = (torch.randn(B, G, Tp, cg, generator=g) * 1.5).to(BF)
+    bias = torch.randn(D, generator=g) * 0.3
+    valid_d = _dev(valid)
+    rev = ops.reverse_rows_bf16(x.cuda().view(B * Tp, D), B, Tp, D)
+    assert torch.equal(rev.view(B, Tp, D).cpu(), x.flip(1))
+    # dx[b, t] = t < valid[b] ? bf16(ds + conv[b, :, Tp - 1 - t, :] regrouped) : 0
+    dx = ops.posconv_dgrad_finish(conv.cuda().view(-1), ds.cuda().view(B * Tp, D), valid_d, B, Tp, D, G).view(B, Tp, D).cpu()
+    want = (conv.flip(2).permute(0, 2, 1, 3).reshape(B, Tp, D).float() + ds.float()).to(BF)
+    for b, v in enumerate(valid):
+        want[b, v:] = 0
+    assert torch.equal(dx, want)
+    for b, v in enumerate(valid):
+        assert bool((dx[b, v:] == 0).all()) and bool((dx[b, :v] != 0).any())
+    # finish-train
+    half_ulp = 2.0 ** -8 * 1.001          # HALF_ULP_BF16 of tests/test_untested_entries_gpu.py
+    xin = x.clone()
+    for b, v in enumerate(valid):
+        xin[b, v:] = 100.0                                                              # must be masked
+    u, s = ops.posconv_finish_train(xin.cuda().view(B * Tp, D), valid_d, conv.cuda().view(-1), bias.cuda(), B, Tp, D, G)
+    u, s = u.cpu().view(B, Tp, D), s.cpu().view(B, Tp, D)
+    u_ref = conv.double().permute(0, 2, 1, 3).reshape(B, Tp, D) + bias.double()
+    assert ((u.double() - u_ref).abs() <= half_ulp * u_ref.abs() + 1e-30).all()
+    xm = xin.double().clone()
+    for b, v in enumerate(valid):
+        xm[b, v:] = 0
+    s_ref = xm + F.gelu(u.double())
+    assert ((s.double() - s_ref).abs() <= half_ulp * s_ref.abs() + 1e-6 * (1 + u.double().abs())).all(), (s.double() - s_ref).abs().max().item()
+    for b, v in enumerate(valid):
+        assert v == Tp or (s[b, v:].double() - F.gelu(u[b, v:].double())).abs().max().item() < 0.02      # rows >= valid: no trace of the 100.0 input

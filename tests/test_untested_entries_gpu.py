@@ -39,7 +39,7 @@ def test_conv0_wgrad_vs_autograd_fp64(B, L, C):
     wav = torch.randn(B, L, generator=g) * 0.3 + 0.1
     du = torch.randn(B, P, C, generator=g).to(BF)
     du[:, T0:] = 1e4
-    dw, db = ops.conv0_wgrad(wav.cuda(), du.cuda().view(B * P, C), C, T0, P)
+    dw, db, _ = ops.conv0_wgrad(wav.cuda(), du.cuda().view(B * P, C), C, T0, P)
     w = torch.zeros(C, 1, 10, dtype=torch.float64, requires_grad=True)
     bias = torch.zeros(C, dtype=torch.float64, requires_grad=True)
     gout = du[:, :T0].double().transpose(1, 2)
