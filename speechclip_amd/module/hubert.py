@@ -420,11 +420,8 @@ class HubertModel(nn.Module):
         tmp = buf("tmp", (M, d), lw, dev)
         tmp2 = buf("tmp2", (M, d), lw, dev)
 
-        def attn(qkv_, att_):
-            if pack is not None:
-                ops.attention_packed(qkv_, B, pack["rows_max"], H, valid_i32, off_i32, out=att_)
-            else:
-                ops.attention(qkv_, B, Tp, H, valid_i32, out=att_)
+        def attn(qkv_, att_, drop=None):      # drop = (p, seed): train mode
+            ops.attention(qkv_, B, pack["rows_max"] if pack is not None else Tp, H, valid_i32, out=att_, row_off_i32=off_i32 if pack is not None else None, drop=drop)
         kept = 0
         # (measured, round 3: moving the residual add out of the out-proj / fc2 epilogues into one LayerNorm(residual + x) pass -- the residual
         #  variant of the GEMM is 20 % slower than the plain one in isolation -- is worth 0.05 ms per step: the bytes only change kernels)
@@ -439,10 +436,7 @@ class HubertModel(nn.Module):
                 STAGE_HOOK("layer%d" % i)
             if not pre_ln and rates:      # [3P fairseq] TransformerSentenceEncoderLayer in train mode: x = LN(x + dropout1(attn(x))); x = LN(x + dropout3(fc2(dropout2(act(fc1 x)))))
                 ops.gemm(h, L["wqkv"], L["bqkv"], out=qkv)
-                if pack is not None:
-                    ops.attention_packed(qkv, B, pack["rows_max"], H, valid_i32, off_i32, out=att, drop_p=rates["attention"], seed=next_seed())
-                else:
-                    ops.attention_dropout(qkv, B, Tp, H, valid_i32, rates["attention"], next_seed(), out=att)
+                attn(qkv, att, (rates["attention"], next_seed()))
                 ops.gemm(att, L["wo"], L["bo"], out=tmp)
                 ops.dropout_add_layernorm(tmp, h, *L["ln1"], rates["hidden"], next_seed(), out=tmp2)
                 ops.gemm(tmp2, L["w1"], L["b1"], ACT_GELU, out=ffn)

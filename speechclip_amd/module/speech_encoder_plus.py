@@ -297,8 +297,10 @@ FairseqSpeechEncoder_Hubert._pack_plan = _pack_plan
 
 def _forward_finetune(self, padded, lens, feat_select_idx, return_hidden_states, drop_seed=None):
     """Training forward with encoder layers L0.. as ONE autograd node (train_hubert.HubertLayersTrainFn): the frozen part below the lowest
-    trainable layer runs on the eval path, the layer mix carries the gradient to the hidden states (WeightedSumTrainFn)."""
-    from ..train_hubert import HubertLayersTrainFn, WeightedSumTrainFn, layer_params
+    trainable layer runs on the eval path (whole-encoder training: the front end is an autograd node too), the layer mix carries the gradient to
+    the hidden states (WeightedSumTrainFn).  One body for both row layouts: every tensor below has M rows, utterance b owning `rows` of them from
+    row b * Tp (padded) or pack["row_off"][b] (padding-free: M = sum_b rows_b); [B, T, d] is restored at the boundary only (`frames`)."""
+    from ..train_hubert import HubertLayersTrainFn, UnpackRowsFn, WeightedSumTrainFn, layer_params
     if feat_select_idx != FEAT_SELECT_IDX_WEIGHTED_SUM_MODE:
         raise NotImplementedError("fine-tuning is wired for feat_select_idx = weighted_sum (every shipped config)")
     enc = self.encoder
@@ -306,107 +308,65 @@ def _forward_finetune(self, padded, lens, feat_select_idx, return_hidden_states,
     dev = padded.device
     L0, nl = self.train_layers[0], cfg.encoder_layers
     B, d = padded.shape[0], cfg.encoder_embed_dim
+    # ---- the row layout: the SC_VARLEN_PACK=0|1|auto rule of the frozen forward (`_pack_plan`)
+    pack = self._pack_plan(padded, lens)
+    if self.train_front and os.environ.get("SC_VARLEN_PACK", "auto") != "1":
+        pack = None      # whole-encoder training: `auto` stays padded until packing is measured faster on it (DESIGN section 3.4); SC_VARLEN_PACK=1 opts in
+    T0, T, P0, Tp = enc.frame_geometry(padded.shape[1])
+    valid = enc.valid_frames(lens, padded.shape[1], T)
+    M, rows, off, pack_kw = B * Tp, Tp, None, {}
+    if pack is not None:
+        M, rows, off = pack["total"], pack["rows_max"], ops.dev_ints(pack["row_off"], torch.int32, dev)
+        pack_kw = dict(pack=dict(row_off=off, rows_max=rows, total=M, scale0=pack["scale0"]))
+    valid_dev = ops.dev_ints(valid, torch.int32, dev)
+
+    def frames(x, crop=True):
+        """[.., M, d] rows -> the reference's [.., B, T, d]: a view of the padded rows ([.., B, Tp, d] without `crop`), a copy of the packed ones (zeros
+        beyond each utterance, the halo row left out; differentiable: forward sc_unpack_rows, backward sc_pack_rows)."""
+        if pack is None:
+            x = x.view(*x.shape[:-2], B, Tp, d)
+            return x[..., :T, :] if crop else x
+        return UnpackRowsFn.apply(x, off, B, T, 1) if x.requires_grad else ops.unpack_rows(x, off, B, T, halo=1)
+
+    # ---- hidden states 0 .. L0 (train-mode dropouts: the frozen layers below L0 through the engine, the trained nodes through their own masks)
     if self.train_front:          # the wave -> hidden state 0 as an autograd node too (train_front.HubertFront[LN]TrainFn)
         from ..train_front import HubertFrontLNTrainFn, HubertFrontTrainFn, front_params, front_params_ln
-        T0, T, P0, Tp = enc.frame_geometry(padded.shape[1])
-        valid = enc.valid_frames(lens, padded.shape[1], T)
         fmeta = dict(conv_layers=[tuple(c) for c in cfg.conv_layers], T0=T0, P0=P0, Tp=Tp, d=d, G=cfg.conv_pos_groups, Kw=cfg.conv_pos,
-                     grad_mult=float(enc.feature_grad_mult), normalize=bool(cfg.normalize))
-        # Padding-free whole-encoder training: the `_pack_plan` decision of the frozen forward and layer fine-tuning under SC_VARLEN_PACK=1; when it
-        # packs, the front end, every layer and the layer mix run on sum_b rows_b rows and [B, T, d] is restored at the boundary only.
-        pack = self._pack_plan(padded, lens)
-        if pack is not None and os.environ.get("SC_VARLEN_PACK", "auto") != "1":
-            pack = None      # `auto` stays padded for this mode until packing is measured faster on it; SC_VARLEN_PACK=1 opts in
-        if pack is not None:
-            off = ops.dev_ints(pack["row_off"], torch.int32, dev)
-            fmeta["pack"] = dict(row_off=off, rows_max=pack["rows_max"], total=pack["total"], scale0=pack["scale0"])
-        valid_dev = ops.dev_ints(valid, torch.int32, dev)
+                     grad_mult=float(enc.feature_grad_mult), normalize=bool(cfg.normalize), **pack_kw)
         if cfg.layer_norm_first:
-            h_front = HubertFrontLNTrainFn.apply(fmeta, padded.contiguous(), ops.dev_ints(lens, torch.int32, dev), valid_dev, *front_params_ln(enc))
+            h_in = HubertFrontLNTrainFn.apply(fmeta, padded.contiguous(), ops.dev_ints(lens, torch.int32, dev), valid_dev, *front_params_ln(enc))
         else:
             if drop_seed is not None:
                 r = enc.dropout_rates()
                 fmeta["drop"] = dict(features=r["features"], hidden=r["hidden"], seed=int(drop_seed))
-            h_front = HubertFrontTrainFn.apply(fmeta, padded.contiguous(), valid_dev, *front_params(enc))      # [B*Tp, d] ([total, d] when packed)
-        if pack is not None:
-            return self._forward_finetune_packed(padded, lens, return_hidden_states, drop_seed, pack, h_front=h_front)
-        hidden = None
+            h_in = HubertFrontTrainFn.apply(fmeta, padded.contiguous(), valid_dev, *front_params(enc))      # [M, d]
+        below = h_in.view(1, M, d)
     else:
-        # Padding-free fine-tuning: the frozen layers below L0, the trained layers and the layer mix all run on sum_b rows_b packed rows; the reference's
-        # [B, T, d] layout is restored at the boundary only.  Same SC_VARLEN_PACK=0|1|auto rule as the frozen forward (`_pack_plan`).
-        pack = self._pack_plan(padded, lens)
-        if pack is not None:
-            return self._forward_finetune_packed(padded, lens, return_hidden_states, drop_seed, pack)
-        # (train-mode dropouts: the frozen layers below L0 through the engine, the trained nodes through their own masks)
-        hidden, T, Tp, valid = enc.extract_all_layers(padded, lens, stop_layer=L0, dropout_seed=drop_seed)        # hidden[0 .. L0] are valid
-    M = B * Tp
+        hidden = enc.extract_all_layers(padded, lens, stop_layer=L0, dropout_seed=drop_seed, pack=pack)[0]        # hidden[0 .. L0] are valid
+        below = hidden[:L0 + 1].reshape(L0 + 1, M, d).detach()
+        h_in = hidden[L0].reshape(M, d).clone()      # the engine's hidden buffer is a reused workspace: the autograd node keeps its own copy
+    # ---- layers L0 .. as one node, the layer mix
     params = []
     for i in range(L0, nl):
         params += layer_params(enc.encoder.layers[i])
-    meta = dict(B=B, Tp=Tp, H=cfg.encoder_attention_heads, eps=1e-5, train=[i in self.train_layers for i in range(L0, nl)],
-                pre_ln=bool(cfg.layer_norm_first))
+    meta = dict(B=B, Tp=rows, H=cfg.encoder_attention_heads, eps=1e-5, train=[i in self.train_layers for i in range(L0, nl)],
+                pre_ln=bool(cfg.layer_norm_first), **pack_kw)
     if drop_seed is not None:
         r = enc.dropout_rates()
         meta["drop"] = dict(hidden=r["hidden"], attention=r["attention"], activation=r["activation"], seed=(int(drop_seed) * 2654435761 + 97) & 0x7fffffff)
-    # (the engine's hidden buffer is a reused workspace: the autograd node keeps its own copy)
-    h_in = h_front if self.train_front else hidden[L0].reshape(M, d).clone()
-    hi = HubertLayersTrainFn.apply(meta, h_in, ops.dev_ints(valid, torch.int32, dev), *params)      # [nl - L0, M, d]
-    below = h_front.view(1, M, d) if self.train_front else hidden[:L0 + 1].reshape(L0 + 1, M, d).detach()
-    hidden_all = torch.cat([below, hi], 0)
+    hi = HubertLayersTrainFn.apply(meta, h_in, valid_dev, *params)      # [nl - L0, M, d]
+    hidden_all = torch.cat([below, hi], 0)                              # [nl + 1, M, d]
     ws = self.weightedsum_layer
-    mixed = WeightedSumTrainFn.apply(hidden_all, ws.weights, ws.normalize_features).view(B, Tp, d)[:, :T]
-    mixed._mix_src = (hidden_all.detach().view(nl + 1, B, Tp, d), ws)                  # the mix weights' gradient comes out of the head's backward
+    mixed = frames(WeightedSumTrainFn.apply(hidden_all, ws.weights, ws.normalize_features))
+    mixed._mix_src = (frames(hidden_all.detach(), crop=False), ws)      # the mix weights' gradient comes out of the head's backward
     feat_len = ops.dev_ints([min(round(l / self.downsample_rate), T) for l in lens], torch.long, dev).clone()
     out = [mixed, feat_len]
-    if return_hidden_states:
-        out.append(tuple(hidden_all[i].view(B, Tp, d)[:, :T] for i in range(nl + 1)))
+    if return_hidden_states:       # views / unpacked copies of hidden_all, attached to the trained layers' autograd node
+        out.append(tuple(frames(hidden_all[i]) for i in range(nl + 1)))
     return tuple(out)
 
 
 FairseqSpeechEncoder_Hubert._forward_finetune = _forward_finetune
-
-
-def _forward_finetune_packed(self, padded, lens, return_hidden_states, drop_seed, pack, h_front=None):
-    """_forward_finetune over packed rows (pack = packed_geometry): utterance b owns rows pack["row_off"][b] .. of every tensor.  The attention of the trained
-    layers runs on sc_attention_fwd_packed / sc_attention_bwd_packed; the mixed frames go back to [B, T, d] through a differentiable unpack (forward
-    sc_unpack_rows with halo = 1, backward sc_pack_rows), so the heads see what the frozen packed path hands them.  h_front (whole-encoder training): hidden
-    state 0 [total, d] from the packed front-end node, attached to the graph; every layer trains on top of it."""
-    from ..train_hubert import HubertLayersTrainFn, UnpackRowsFn, WeightedSumTrainFn, layer_params
-    enc = self.encoder
-    cfg = enc.cfg
-    dev = padded.device
-    L0, nl = self.train_layers[0], cfg.encoder_layers
-    B, d = padded.shape[0], cfg.encoder_embed_dim
-    if h_front is None:
-        hidden, T, _, valid = enc.extract_all_layers(padded, lens, stop_layer=L0, dropout_seed=drop_seed, pack=pack)      # [L0 + 1, total, d]
-    else:
-        T, valid = pack["T"], pack["valid"]
-    M = pack["total"]
-    off = ops.dev_ints(pack["row_off"], torch.int32, dev)
-    params = []
-    for i in range(L0, nl):
-        params += layer_params(enc.encoder.layers[i])
-    meta = dict(B=B, Tp=pack["rows_max"], H=cfg.encoder_attention_heads, eps=1e-5, train=[i in self.train_layers for i in range(L0, nl)],
-                pre_ln=bool(cfg.layer_norm_first), pack=dict(row_off=off, rows_max=pack["rows_max"], total=M))
-    if drop_seed is not None:
-        r = enc.dropout_rates()
-        meta["drop"] = dict(hidden=r["hidden"], attention=r["attention"], activation=r["activation"], seed=(int(drop_seed) * 2654435761 + 97) & 0x7fffffff)
-    h_in = hidden[L0].clone() if h_front is None else h_front      # the engine's hidden buffer is a reused workspace
-    hi = HubertLayersTrainFn.apply(meta, h_in, ops.dev_ints(valid, torch.int32, dev), *params)      # [nl - L0, total, d]
-    below = hidden[:L0 + 1].detach() if h_front is None else h_front.view(1, M, d)
-    hidden_all = torch.cat([below, hi], 0)                                                           # [nl + 1, total, d]
-    ws = self.weightedsum_layer
-    mixed = UnpackRowsFn.apply(WeightedSumTrainFn.apply(hidden_all, ws.weights, ws.normalize_features), off, B, T, 1)          # [B, T, d]
-    states = ops.unpack_rows(hidden_all.detach(), off, B, T, halo=1)                                 # [nl + 1, B, T, d], zeros beyond each utterance
-    mixed._mix_src = (states, ws)                                                                     # the mix weights' gradient comes out of the head's backward
-    feat_len = ops.dev_ints([min(round(l / self.downsample_rate), T) for l in lens], torch.long, dev).clone()
-    out = [mixed, feat_len]
-    if return_hidden_states:       # as on the padded layout: views of hidden_all, attached to the trained layers' autograd node
-        out.append(tuple(UnpackRowsFn.apply(hidden_all[i], off, B, T, 1) for i in range(nl + 1)))
-    return tuple(out)
-
-
-FairseqSpeechEncoder_Hubert._forward_finetune_packed = _forward_finetune_packed
 
 
 class S3prlSpeechEncoderPlus(nn.Module):

@@ -231,31 +231,38 @@ def wave_layernorm(wav, lens_i32, eps=1e-5):
     return out
 
 
-def attention(qkv, B, T, H, klens_i32=None, out=None, scale=None, causal=False):
-    """qkv: bf16 (or IEEE half: SC_ATTN_F16) [B*T, 3*H*64] packed (q|k|v); returns the same format [B*T, H*64]."""
-    _need_cuda(qkv)
+def attention(qkv, B, T, H, klens_i32=None, out=None, scale=None, causal=False, row_off_i32=None, drop=None):
+    """qkv: bf16 (or IEEE half: SC_ATTN_F16) [rows, 3*H*64] packed (q|k|v); returns the same format [rows, H*64].  row_off_i32 None: uniform rows
+    (rows = B*T); else packed rows, utterance b at rows row_off[b] .. (at most T each).  drop = (p, seed): dropout on the attention probabilities
+    (train mode; p == 0 is the plain arithmetic).  scale / causal exist on the plain uniform entry only, IEEE half not on the uniform dropout one."""
+    _need_cuda(qkv, klens_i32, row_off_i32)
     D = H * 64
-    assert qkv.dtype in (bf16, torch.float16) and qkv.shape == (B * T, 3 * D) and qkv.is_contiguous()
+    total = B * T if row_off_i32 is None else qkv.shape[0]
+    assert qkv.dtype in (bf16, torch.float16) and qkv.shape == (total, 3 * D) and qkv.is_contiguous()
+    f16 = qkv.dtype == torch.float16
+    if (scale is not None or causal) and (row_off_i32 is not None or drop is not None):
+        raise _lib.SpeechClipHipError("attention: scale / causal are served on uniform rows without dropout only")
+    if f16 and drop is not None and row_off_i32 is None:
+        raise _lib.SpeechClipHipError("attention: dropout on uniform rows is bf16 only")
     if out is None:
-        out = torch.empty(B * T, D, device=qkv.device, dtype=qkv.dtype)
+        out = torch.empty(total, D, device=qkv.device, dtype=qkv.dtype)
     assert out.dtype == qkv.dtype
-    esz = 2
-    check(lib().sc_attention_fwd(qkv.data_ptr(), qkv.data_ptr() + D * esz, qkv.data_ptr() + 2 * D * esz, ptr(out), ptr(klens_i32),
-                                 B, H, T, 64, 3 * D, D, 0.125 if scale is None else scale, (ATTN_CAUSAL if causal else 0) | (ATTN_F16 if qkv.dtype == torch.float16 else 0),
-                                 stream()), "sc_attention_fwd")
+    q, k, v = qkv.data_ptr(), qkv.data_ptr() + D * 2, qkv.data_ptr() + 2 * D * 2
+    p_, seed = (float(drop[0]), int(drop[1]) & 0xffffffff) if drop is not None else (0.0, 0)
+    if row_off_i32 is not None:
+        check(lib().sc_attention_fwd_packed(q, k, v, ptr(out), ptr(klens_i32), ptr(row_off_i32), B, H, T, total, 64, 3 * D, D, 0.125, p_, seed,
+                                            ATTN_F16 if f16 else 0, stream()), "sc_attention_fwd_packed")
+    elif drop is not None:
+        check(lib().sc_attention_fwd_dropout(q, k, v, ptr(out), ptr(klens_i32), B, H, T, 64, 3 * D, D, 0.125, 0, p_, seed, stream()), "sc_attention_fwd_dropout")
+    else:
+        check(lib().sc_attention_fwd(q, k, v, ptr(out), ptr(klens_i32), B, H, T, 64, 3 * D, D, 0.125 if scale is None else scale,
+                                     (ATTN_CAUSAL if causal else 0) | (ATTN_F16 if f16 else 0), stream()), "sc_attention_fwd")
     return out
 
 
 def attention_dropout(qkv, B, T, H, klens_i32, drop_p, seed, out=None):
-    """ops.attention with dropout on the attention probabilities (train-mode frozen encoder); drop_p == 0 is the plain kernel."""
-    _need_cuda(qkv)
-    D = H * 64
-    assert qkv.dtype == bf16 and qkv.shape == (B * T, 3 * D) and qkv.is_contiguous()
-    if out is None:
-        out = torch.empty(B * T, D, device=qkv.device, dtype=bf16)
-    check(lib().sc_attention_fwd_dropout(qkv.data_ptr(), qkv.data_ptr() + D * 2, qkv.data_ptr() + 2 * D * 2, ptr(out), ptr(klens_i32), B, H, T, 64,
-                                         3 * D, D, 0.125, 0, float(drop_p), int(seed) & 0xffffffff, stream()), "sc_attention_fwd_dropout")
-    return out
+    """ops.attention(..., drop=(drop_p, seed)) on uniform rows (kept for its callers)."""
+    return attention(qkv, B, T, H, klens_i32, out=out, drop=(drop_p, seed))
 
 
 def dropout_bf16(x, drop_p, seed, residual=None, out=None):
@@ -471,18 +478,8 @@ def posconv_packed(x, valid_i32, row_off_i32, wg, bias, gamma, beta, B, rows_max
 
 
 def attention_packed(qkv, B, rows_max, H, klens_i32, row_off_i32, out=None, drop_p=0.0, seed=0):
-    """ops.attention / ops.attention_dropout over packed rows: qkv bf16 [total_rows, 3*H*64]."""
-    _need_cuda(qkv, klens_i32, row_off_i32)
-    D = H * 64
-    total = qkv.shape[0]
-    assert qkv.dtype in (bf16, torch.float16) and qkv.shape == (total, 3 * D) and qkv.is_contiguous()
-    if out is None:
-        out = torch.empty(total, D, device=qkv.device, dtype=qkv.dtype)
-    assert out.dtype == qkv.dtype
-    check(lib().sc_attention_fwd_packed(qkv.data_ptr(), qkv.data_ptr() + D * 2, qkv.data_ptr() + 2 * D * 2, ptr(out), ptr(klens_i32), ptr(row_off_i32),
-                                        B, H, rows_max, total, 64, 3 * D, D, 0.125, float(drop_p), int(seed) & 0xffffffff,
-                                        ATTN_F16 if qkv.dtype == torch.float16 else 0, stream()), "sc_attention_fwd_packed")
-    return out
+    """ops.attention over packed rows: qkv [total_rows, 3*H*64] (kept for its callers)."""
+    return attention(qkv, B, rows_max, H, klens_i32, out=out, row_off_i32=row_off_i32, drop=(drop_p, seed))
 
 
 def unpack_rows(src, row_off_i32, B, T_out, halo=0):

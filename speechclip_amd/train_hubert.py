@@ -9,8 +9,9 @@ hidden states (through `WeightedSumLayer`, weighted_sum.py:26-45) and has to tra
 with fused epilogues, flash attention, LayerNorm) keeping what the backward needs; backward in bf16 with fp32 accumulation:
   dX = dY W            sc_gemm_bf16 on transposed bf16 weight copies (residual branches added in the epilogue)
   dW = dY^T X          sc_transpose_bf16 of both operands + ONE split-K sc_gemm_bf16_batched + sc_colsum over the splits (fp32 result)
-  attention            S = Q K^T and dP = dO V^T recomputed per head (batched MFMA GEMMs), sc_attn_softmax_bwd -> P, dS, then dQ = dS K,
-                       dK = dS^T Q, dV = P^T dO as batched GEMMs over transposed operands (key-padding mask = the forward's klens)
+  attention            padded rows: the image chain (`attention_bwd`) -- sc_attn_bwd_probs recomputes S = Q K^T and dP = dO V^T on the MFMA and writes
+                       P and dS [Lp, Lp] per (utterance, head), then dQ = dS K, dK = dS^T Q, dV = P^T dO as two-level batched GEMMs over transposed
+                       copies; packed rows: ONE fused kernel, sc_attention_bwd_packed (`attention_bwd_packed`), no image (key mask = the forward's klens)
   LayerNorm / GELU     sc_layernorm_bwd_bf16 (+ partial column sums -> dgamma, dbeta), sc_gelu_bwd_bf16 (fc1's pre-activation is recomputed)
 Post-LN layers (HuBERT-base) and, with meta["pre_ln"], pre-LN layers on an fp32 residual stream (HuBERT-large, `unfreeze_layers` / `reinit_layers`
 only: its LayerNorm-extractor front end has no backward here).  meta["drop"] = dict(hidden, attention, activation, seed) applies the
@@ -115,28 +116,147 @@ def _pack_of(meta, dev):
     return off, int(pk["rows_max"]), int(pk["total"]), int(pk.get("scale0", 0))
 
 
-def _qkv_rows(pk, M, Lp, Tp, d, dev):
+def _qkv_rows(pk, M, Tp, d, dev):
     """The q | k | v buffer of one layer: M rows, plus zeroed slack rows on the padded layout (the image form of the backward reads Lp keys per utterance)."""
     if pk is not None:
         return torch.empty(M, 3 * d, device=dev, dtype=BF)
-    qkv = torch.empty(M + (Lp - Tp), 3 * d, device=dev, dtype=BF)
+    qkv = torch.empty(M + (-(-Tp // 64) * 64 - Tp), 3 * d, device=dev, dtype=BF)
     qkv[M:].zero_()          # slack rows: the backward's S / dP products read Lp keys per utterance
     return qkv
 
 
 def _attn_fwd(pk, qkv, M, B, Tp, H, valid_i32, drop=None):
     """drop = (p, seed): the train-mode form (dropout on the attention probabilities)."""
-    if pk is not None:
-        return ops.attention_packed(qkv, B, pk[1], H, valid_i32, pk[0], drop_p=drop[0] if drop else 0.0, seed=drop[1] if drop else 0)
-    if drop is not None:
-        return ops.attention_dropout(qkv[:M], B, Tp, H, valid_i32, drop[0], drop[1])
-    return ops.attention(qkv[:M], B, Tp, H, valid_i32)
+    return ops.attention(qkv[:M], B, Tp, H, valid_i32, row_off_i32=None if pk is None else pk[0], drop=drop)
 
 
 def _attn_bwd(pk, qkv, att, datt, B, Tp, H, valid_i32, drop=None):
     if pk is not None:
         return attention_bwd_packed(qkv, att, datt, B, pk[1], H, valid_i32, pk[0], drop)
     return attention_bwd(qkv, att, datt, B, Tp, H, valid_i32, drop)
+
+
+def _site_seeds(seed, count):
+    """`count` dropout-site seeds from one forward's seed, in forward order (the LCG of the frozen forward's next_seed)."""
+    s0, seeds = int(seed) & 0x7fffffff, []
+    for _ in range(count):
+        s0 = (s0 * 1103515245 + 12345) & 0x7fffffff
+        seeds.append(s0)
+    return seeds
+
+
+# One layer, forward: (h, the converted q|k|v weight and bias, the layer's other 10 parameters, pk, (B, Tp, H, eps), valid_i32, out = hidden[li],
+# drop, this layer's 4 site seeds) -> the 7 tensors its backward reads; the layer's output is written into `out`.
+
+def _layer_fwd_post_ln(h, wqkv, bqkv, p, pk, shape, valid_i32, out, drop, seeds):
+    B, Tp, H, eps = shape
+    M, d = h.shape
+    ow, ob, g1, b1n, w1, b1, w2, b2, g2, b2n = p
+    qkv = _qkv_rows(pk, M, Tp, d, h.device)
+    ops.gemm(h, wqkv, bqkv, out=qkv[:M])
+    if drop is None:
+        att = _attn_fwd(pk, qkv, M, B, Tp, H, valid_i32)
+        y1 = ops.gemm(att, _w16(ow), _f32(ob), residual=h)
+        x1 = ops.layernorm(y1, _f32(g1), _f32(b1n), eps)
+        hm = ops.gemm(x1, _w16(w1), _f32(b1), ACT_GELU)
+        y2 = ops.gemm(hm, _w16(w2), _f32(b2), residual=x1)
+    else:       # x = LN(x + dropout1(attn(x)));  x = LN(x + dropout3(fc2(dropout2(gelu(fc1 x)))))
+        sa, s1, s2, s3 = seeds
+        att = _attn_fwd(pk, qkv, M, B, Tp, H, valid_i32, (drop["attention"], sa))
+        y1 = ops.gemm(att, _w16(ow), _f32(ob))
+        ops.dropout_bf16(y1, drop["hidden"], s1, residual=h, out=y1)
+        x1 = ops.layernorm(y1, _f32(g1), _f32(b1n), eps)
+        hm = ops.gemm(x1, _w16(w1), _f32(b1), ACT_GELU)
+        if drop["activation"] > 0:
+            ops.dropout_bf16(hm, drop["activation"], s2, out=hm)
+        y2 = ops.gemm(hm, _w16(w2), _f32(b2))
+        ops.dropout_bf16(y2, drop["hidden"], s3, residual=x1, out=y2)
+    ops.layernorm(y2, _f32(g2), _f32(b2n), eps, out=out)
+    return [h, qkv, att, y1, x1, hm, y2]
+
+
+def _layer_fwd_pre_ln(h, wqkv, bqkv, p, pk, shape, valid_i32, out, drop, seeds):
+    """Pre-LN layers ([3P fairseq] layer_norm_first, HuBERT-large): x += attn(LN1 x); x += fc2(gelu(fc1(LN2 x))) on an fp32 residual stream.
+    h / out are f32; the saved copies of the stream (LayerNorm inputs of the backward) are bf16.  The large checkpoint's dropouts are 0."""
+    B, Tp, H, eps = shape
+    M, d = h.shape
+    ow, ob, g1, b1n, w1, b1, w2, b2, g2, b2n = p
+    t1 = ops.layernorm(h, _f32(g1), _f32(b1n), eps)                                   # bf16
+    qkv = _qkv_rows(pk, M, Tp, d, h.device)
+    ops.gemm(t1, wqkv, bqkv, out=qkv[:M])
+    att = _attn_fwd(pk, qkv, M, B, Tp, H, valid_i32)
+    xmid = ops.gemm(att, _w16(ow), _f32(ob), residual=h, out_f32=True)
+    t2 = ops.layernorm(xmid, _f32(g2), _f32(b2n), eps)
+    hm = ops.gemm(t2, _w16(w1), _f32(b1), ACT_GELU)
+    ops.gemm(hm, _w16(w2), _f32(b2), residual=xmid, out=out, out_f32=True)
+    return [h.to(BF), qkv, att, xmid.to(BF), t1, hm, t2]
+
+
+# One layer, backward: (g = gradient of the layer's output (bf16), its 7 saved tensors, its 16 parameters, pk, (B, Tp, H, eps), valid_i32, want, drop,
+# its 4 site seeds) -> (dh, the operands of the layer's parameter gradients in `_param_grads` order, or None without `want`).
+
+def _layer_bwd_post_ln(g, acts, p, pk, shape, valid_i32, want, drop, seeds):
+    B, Tp, H, eps = shape
+    h, qkv, att, y1, x1, hm, y2 = acts
+    qw, qb, kw, kb, vw, vb, ow, ob, g1, b1n, w1, b1, w2, b2, g2, b2n = p
+    sa, s1, s2, s3 = seeds
+    # x2 = LN2(y2)
+    dy2r, dg2, db2n = ops.layernorm_bwd_bf16(y2, g, _f32(g2), eps, want)
+    # y2 = dropout3(hm W2^T + b2) + x1: the residual branch takes dy2r as it is, the fc2 branch the masked gradient
+    dy2 = dy2r if drop is None else ops.dropout_bf16(dy2r, drop["hidden"], s3)
+    dhm = ops.gemm(dy2, _w16(w2.t()))                                  # [M, ffn] = dy2 W2
+    if drop is not None and drop["activation"] > 0:
+        ops.dropout_bf16(dhm, drop["activation"], s2, out=dhm)
+    u = ops.gemm(x1, _w16(w1), _f32(b1))                               # fc1's pre-activation, recomputed (not kept by the forward)
+    du = ops.gelu_bwd_bf16(u, dhm)
+    del u, dhm
+    # u = x1 W1^T + b1 ; x1 also feeds the residual of fc2
+    dx1 = ops.gemm(du, _w16(w1.t()), residual=dy2r)                    # [M, d] = du W1 + dy2 (unmasked: the residual path)
+    # x1 = LN1(y1)
+    dy1r, dg1, db1n = ops.layernorm_bwd_bf16(y1, dx1, _f32(g1), eps, want)
+    # y1 = dropout1(att Wo^T + bo) + h
+    dy1 = dy1r if drop is None else ops.dropout_bf16(dy1r, drop["hidden"], s1)
+    datt = ops.gemm(dy1, _w16(ow.t()))
+    dqkv = _attn_bwd(pk, qkv, att, datt, B, Tp, H, valid_i32, None if drop is None or drop["attention"] <= 0 else (drop["attention"], sa))
+    wqkv = torch.cat([qw, kw, vw], 0)
+    dh = ops.gemm(dqkv, _w16(wqkv.t()), residual=dy1r)                 # [M, d] = dqkv Wqkv + dy1 (unmasked: the residual path)
+    return dh, (dqkv, h, dy1, att, du, x1, dy2, hm, dg1, db1n, dg2, db2n) if want else None
+
+
+def _layer_bwd_pre_ln(g, acts, p, pk, shape, valid_i32, want, drop, seeds):
+    B, Tp, H, eps = shape
+    h16, qkv, att, xmid16, t1, hm, t2 = acts
+    qw, qb, kw, kb, vw, vb, ow, ob, g1, b1n, w1, b1, w2, b2, g2, b2n = p
+    # out = xmid + fc2(gelu(fc1(t2))),  t2 = LN2(xmid)
+    dhm = ops.gemm(g, _w16(w2.t()))
+    u = ops.gemm(t2, _w16(w1), _f32(b1))
+    du = ops.gelu_bwd_bf16(u, dhm)
+    del u, dhm
+    dt2 = ops.gemm(du, _w16(w1.t()))
+    dxm, dg2, db2n = ops.layernorm_bwd_bf16(xmid16, dt2, _f32(g2), eps, want)
+    ops.axpy_bf16(dxm, g, 1.0)                                 # + the residual path
+    # xmid = h + out_proj(attn(qkv(t1))),  t1 = LN1(h)
+    datt = ops.gemm(dxm, _w16(ow.t()))
+    dqkv = _attn_bwd(pk, qkv, att, datt, B, Tp, H, valid_i32)
+    wqkv = torch.cat([qw, kw, vw], 0)
+    dt1 = ops.gemm(dqkv, _w16(wqkv.t()))
+    dh, dg1, db1n = ops.layernorm_bwd_bf16(h16, dt1, _f32(g1), eps, want)
+    ops.axpy_bf16(dh, dxm, 1.0)
+    return dh, (dqkv, t1, dxm, att, du, t2, g, hm, dg1, db1n, dg2, db2n) if want else None
+
+
+def _param_grads(grads, base, dqkv, x_qkv, dyo, att, du, x_fc1, dy2, hm, dg1, db1n, dg2, db2n):
+    """The 16 parameter gradients of one layer into grads[base ..] (PER_LAYER order), from each projection's output gradient and input."""
+    d = att.shape[1]
+    dwqkv = wgrad(dqkv, x_qkv)
+    dbqkv = ops.colsum_bf16(dqkv)
+    grads[base + 0], grads[base + 2], grads[base + 4] = dwqkv[:d], dwqkv[d:2 * d], dwqkv[2 * d:]
+    grads[base + 1], grads[base + 3], grads[base + 5] = dbqkv[:d], dbqkv[d:2 * d], dbqkv[2 * d:]
+    grads[base + 6], grads[base + 7] = wgrad(dyo, att), ops.colsum_bf16(dyo)
+    grads[base + 8], grads[base + 9] = dg1, db1n
+    grads[base + 10], grads[base + 11] = wgrad(du, x_fc1), ops.colsum_bf16(du)
+    grads[base + 12], grads[base + 13] = wgrad(dy2, hm), ops.colsum_bf16(dy2)
+    grads[base + 14], grads[base + 15] = dg2, db2n
 
 
 class UnpackRowsFn(torch.autograd.Function):
@@ -153,194 +273,58 @@ class UnpackRowsFn(torch.autograd.Function):
 
 
 class HubertLayersTrainFn(torch.autograd.Function):
-    """hidden bf16 [n, M, d] = outputs of post-LN layers L0 .. L0+n-1 applied to h_in.
-    args: meta (B, Tp, H, eps, train (list of bool per layer: compute parameter gradients)), h_in bf16 [M, d], valid_i32 [B], then 16 tensors per layer.
+    """hidden [n, M, d] = outputs of layers L0 .. L0+n-1 applied to h_in: post-LN layers on bf16, with meta["pre_ln"] pre-LN layers on f32.
+    args: meta (B, Tp, H, eps, train (list of bool per layer: compute parameter gradients)), h_in [M, d], valid_i32 [B], then 16 tensors per layer.
     meta["pack"] = dict(row_off, rows_max, total): the padding-free layout -- M = total rows, utterance b at rows row_off[b] .., Tp = rows_max; attention runs
-    on ops.attention_packed forward and on the fused sc_attention_bwd_packed backward (every other kernel of a layer is row-wise)."""
+    on the packed ops.attention forward and on the fused sc_attention_bwd_packed backward (every other kernel of a layer is row-wise)."""
 
     @staticmethod
     def forward(ctx, meta, h_in, valid_i32, *params):
-        B, Tp, H, eps = meta["B"], meta["Tp"], meta["H"], meta["eps"]
+        shape = B, Tp, H, _ = meta["B"], meta["Tp"], meta["H"], meta["eps"]
         n = len(params) // PER_LAYER
         M, d = h_in.shape
-        dev = h_in.device
-        pk = _pack_of(meta, dev)         # packed rows: M = sum_b rows_b, Tp = the longest utterance's rows
+        pk = _pack_of(meta, h_in.device)         # packed rows: M = sum_b rows_b, Tp = the longest utterance's rows
         assert M == (B * Tp if pk is None else pk[2]) and d == H * 64
-        Lp = -(-Tp // 64) * 64
         pre_ln = bool(meta.get("pre_ln", False))
-        if pre_ln:
-            return HubertLayersTrainFn._forward_pre_ln(ctx, meta, h_in, valid_i32, params)
-        hidden = torch.empty(n, M, d, device=dev, dtype=BF)
-        saved = []
         drop = meta.get("drop")
-        seeds = []
-        if drop is not None:
-            s0 = int(drop["seed"]) & 0x7fffffff
-            for _ in range(4 * n):
-                s0 = (s0 * 1103515245 + 12345) & 0x7fffffff
-                seeds.append(s0)
-        h = h_in.detach()
-        for li in range(n):
-            qw, qb, kw, kb, vw, vb, ow, ob, g1, b1n, w1, b1, w2, b2, g2, b2n = params[li * PER_LAYER:(li + 1) * PER_LAYER]
-            wqkv, bqkv = _w16(torch.cat([qw, kw, vw], 0)), _f32(torch.cat([qb, kb, vb], 0))
-            qkv = _qkv_rows(pk, M, Lp, Tp, d, dev)
-            ops.gemm(h, wqkv, bqkv, out=qkv[:M])
-            if drop is None:
-                att = _attn_fwd(pk, qkv, M, B, Tp, H, valid_i32)
-                y1 = ops.gemm(att, _w16(ow), _f32(ob), residual=h)
-                x1 = ops.layernorm(y1, _f32(g1), _f32(b1n), eps)
-                hm = ops.gemm(x1, _w16(w1), _f32(b1), ACT_GELU)
-                y2 = ops.gemm(hm, _w16(w2), _f32(b2), residual=x1)
-            else:       # x = LN(x + dropout1(attn(x)));  x = LN(x + dropout3(fc2(dropout2(gelu(fc1 x)))))
-                sa, s1, s2, s3 = seeds[4 * li:4 * li + 4]
-                att = _attn_fwd(pk, qkv, M, B, Tp, H, valid_i32, (drop["attention"], sa))
-                y1 = ops.gemm(att, _w16(ow), _f32(ob))
-                ops.dropout_bf16(y1, drop["hidden"], s1, residual=h, out=y1)
-                x1 = ops.layernorm(y1, _f32(g1), _f32(b1n), eps)
-                hm = ops.gemm(x1, _w16(w1), _f32(b1), ACT_GELU)
-                if drop["activation"] > 0:
-                    ops.dropout_bf16(hm, drop["activation"], s2, out=hm)
-                y2 = ops.gemm(hm, _w16(w2), _f32(b2))
-                ops.dropout_bf16(y2, drop["hidden"], s3, residual=x1, out=y2)
-            ops.layernorm(y2, _f32(g2), _f32(b2n), eps, out=hidden[li])
-            saved += [h, qkv, att, y1, x1, hm, y2]
-            h = hidden[li]
-        ctx.meta = dict(meta, n=n, seeds=seeds)
-        ctx.valid = valid_i32
-        ctx.save_for_backward(*saved, *[p.detach() for p in params])
-        return hidden
-
-    @staticmethod
-    def _forward_pre_ln(ctx, meta, h_in, valid_i32, params):
-        """Pre-LN layers ([3P fairseq] layer_norm_first, HuBERT-large): x += attn(LN1 x); x += fc2(gelu(fc1(LN2 x))) on an fp32 residual stream.
-        h_in / hidden are f32; the saved copies of the stream (LayerNorm inputs of the backward) are bf16.  The large checkpoint's dropouts are 0."""
-        B, Tp, H, eps = meta["B"], meta["Tp"], meta["H"], meta["eps"]
-        assert meta.get("drop") is None or not any(v > 0 for k, v in meta["drop"].items() if k != "seed"), "dropout inside pre-LN layers is not built"
-        n = len(params) // PER_LAYER
-        M, d = h_in.shape
-        dev = h_in.device
-        pk = _pack_of(meta, dev)
-        Lp = -(-Tp // 64) * 64
-        hidden = torch.empty(n, M, d, device=dev, dtype=torch.float32)
+        if pre_ln:
+            assert drop is None or not any(v > 0 for k, v in drop.items() if k != "seed"), "dropout inside pre-LN layers is not built"
+            drop = None
+        seeds = _site_seeds(drop["seed"], 4 * n) if drop is not None else []
+        hidden = torch.empty(n, M, d, device=h_in.device, dtype=torch.float32 if pre_ln else BF)
+        layer = _layer_fwd_pre_ln if pre_ln else _layer_fwd_post_ln
         saved = []
-        h = h_in.detach().float().contiguous()
+        h = h_in.detach().float().contiguous() if pre_ln else h_in.detach()
         for li in range(n):
-            qw, qb, kw, kb, vw, vb, ow, ob, g1, b1n, w1, b1, w2, b2, g2, b2n = params[li * PER_LAYER:(li + 1) * PER_LAYER]
+            qw, qb, kw, kb, vw, vb, *rest = params[li * PER_LAYER:(li + 1) * PER_LAYER]
             wqkv, bqkv = _w16(torch.cat([qw, kw, vw], 0)), _f32(torch.cat([qb, kb, vb], 0))
-            t1 = ops.layernorm(h, _f32(g1), _f32(b1n), eps)                                   # bf16
-            qkv = _qkv_rows(pk, M, Lp, Tp, d, dev)
-            ops.gemm(t1, wqkv, bqkv, out=qkv[:M])
-            att = _attn_fwd(pk, qkv, M, B, Tp, H, valid_i32)
-            xmid = ops.gemm(att, _w16(ow), _f32(ob), residual=h, out_f32=True)
-            t2 = ops.layernorm(xmid, _f32(g2), _f32(b2n), eps)
-            hm = ops.gemm(t2, _w16(w1), _f32(b1), ACT_GELU)
-            ops.gemm(hm, _w16(w2), _f32(b2), residual=xmid, out=hidden[li], out_f32=True)
-            saved += [h.to(BF), qkv, att, xmid.to(BF), t1, hm, t2]
+            saved += layer(h, wqkv, bqkv, rest, pk, shape, valid_i32, hidden[li], drop, seeds[4 * li:4 * li + 4])
             h = hidden[li]
-        ctx.meta = dict(meta, n=n, seeds=[])
-        ctx.valid = valid_i32
+        ctx.meta = dict(meta, n=n, seeds=seeds, drop=drop)
+        ctx.valid, ctx.pk = valid_i32, pk
         ctx.save_for_backward(*saved, *[p.detach() for p in params])
         return hidden
-
-    @staticmethod
-    def _backward_pre_ln(ctx, dhidden):
-        m = ctx.meta
-        B, Tp, H, eps, n, train = m["B"], m["Tp"], m["H"], m["eps"], m["n"], m["train"]
-        tensors = ctx.saved_tensors
-        acts, params = tensors[:7 * n], tensors[7 * n:]
-        dhidden = dhidden.to(BF).contiguous()
-        grads = [None] * len(params)
-        g = dhidden[n - 1].clone()                                   # gradient of the residual stream after the top layer (bf16)
-        for li in range(n - 1, -1, -1):
-            h16, qkv, att, xmid16, t1, hm, t2 = acts[7 * li:7 * li + 7]
-            qw, qb, kw, kb, vw, vb, ow, ob, g1, b1n, w1, b1, w2, b2, g2, b2n = params[li * PER_LAYER:(li + 1) * PER_LAYER]
-            want = bool(train[li])
-            M, d = h16.shape
-            # out = xmid + fc2(gelu(fc1(t2))),  t2 = LN2(xmid)
-            dhm = ops.gemm(g, _w16(w2.t()))
-            u = ops.gemm(t2, _w16(w1), _f32(b1))
-            du = ops.gelu_bwd_bf16(u, dhm)
-            del u, dhm
-            dt2 = ops.gemm(du, _w16(w1.t()))
-            dxm, dg2, db2n = ops.layernorm_bwd_bf16(xmid16, dt2, _f32(g2), eps, want)
-            ops.axpy_bf16(dxm, g, 1.0)                                 # + the residual path
-            # xmid = h + out_proj(attn(qkv(t1))),  t1 = LN1(h)
-            datt = ops.gemm(dxm, _w16(ow.t()))
-            dqkv = _attn_bwd(_pack_of(m, datt.device), qkv, att, datt, B, Tp, H, ctx.valid)
-            wqkv = torch.cat([qw, kw, vw], 0)
-            dt1 = ops.gemm(dqkv, _w16(wqkv.t()))
-            dh, dg1, db1n = ops.layernorm_bwd_bf16(h16, dt1, _f32(g1), eps, want)
-            ops.axpy_bf16(dh, dxm, 1.0)
-            if want:
-                dwqkv = wgrad(dqkv, t1)
-                dbqkv = ops.colsum_bf16(dqkv)
-                base = li * PER_LAYER
-                grads[base + 0], grads[base + 2], grads[base + 4] = dwqkv[:d], dwqkv[d:2 * d], dwqkv[2 * d:]
-                grads[base + 1], grads[base + 3], grads[base + 5] = dbqkv[:d], dbqkv[d:2 * d], dbqkv[2 * d:]
-                grads[base + 6], grads[base + 7] = wgrad(dxm, att), ops.colsum_bf16(dxm)
-                grads[base + 8], grads[base + 9] = dg1, db1n
-                grads[base + 10], grads[base + 11] = wgrad(du, t2), ops.colsum_bf16(du)
-                grads[base + 12], grads[base + 13] = wgrad(g, hm), ops.colsum_bf16(g)
-                grads[base + 14], grads[base + 15] = dg2, db2n
-            g = dh
-            if li > 0:
-                ops.axpy_bf16(g, dhidden[li - 1], 1.0)
-        return (None, g.float() if ctx.needs_input_grad[1] else None, None, *grads)
 
     @staticmethod
     def backward(ctx, dhidden):
-        if ctx.meta.get("pre_ln"):
-            return HubertLayersTrainFn._backward_pre_ln(ctx, dhidden)
         m = ctx.meta
-        B, Tp, H, eps, n, train = m["B"], m["Tp"], m["H"], m["eps"], m["n"], m["train"]
+        n, train, drop, pre_ln = m["n"], m["train"], m["drop"], bool(m.get("pre_ln", False))
+        shape = m["B"], m["Tp"], m["H"], m["eps"]
         tensors = ctx.saved_tensors
         acts, params = tensors[:7 * n], tensors[7 * n:]
         dhidden = dhidden.to(BF).contiguous()
         grads = [None] * len(params)
-        g = dhidden[n - 1].clone()                                   # d loss / d (output of the top layer)
+        layer = _layer_bwd_pre_ln if pre_ln else _layer_bwd_post_ln
+        g = dhidden[n - 1].clone()                                   # d loss / d (output of the top layer), bf16 (pre-LN: of the residual stream)
         for li in range(n - 1, -1, -1):
-            h, qkv, att, y1, x1, hm, y2 = acts[7 * li:7 * li + 7]
-            qw, qb, kw, kb, vw, vb, ow, ob, g1, b1n, w1, b1, w2, b2, g2, b2n = params[li * PER_LAYER:(li + 1) * PER_LAYER]
-            want = bool(train[li])
-            M, d = h.shape
-            drop = m.get("drop")
-            sa, s1, s2, s3 = m["seeds"][4 * li:4 * li + 4] if drop is not None else (0, 0, 0, 0)
-            # x2 = LN2(y2)
-            dy2r, dg2, db2n = ops.layernorm_bwd_bf16(y2, g, _f32(g2), eps, want)
-            # y2 = dropout3(hm W2^T + b2) + x1: the residual branch takes dy2r as it is, the fc2 branch the masked gradient
-            dy2 = dy2r if drop is None else ops.dropout_bf16(dy2r, drop["hidden"], s3)
-            dhm = ops.gemm(dy2, _w16(w2.t()))                                  # [M, ffn] = dy2 W2
-            if drop is not None and drop["activation"] > 0:
-                ops.dropout_bf16(dhm, drop["activation"], s2, out=dhm)
-            u = ops.gemm(x1, _w16(w1), _f32(b1))                               # fc1's pre-activation, recomputed (not kept by the forward)
-            du = ops.gelu_bwd_bf16(u, dhm)
-            del u, dhm
-            # u = x1 W1^T + b1 ; x1 also feeds the residual of fc2
-            dx1 = ops.gemm(du, _w16(w1.t()), residual=dy2r)                    # [M, d] = du W1 + dy2 (unmasked: the residual path)
-            # x1 = LN1(y1)
-            dy1r, dg1, db1n = ops.layernorm_bwd_bf16(y1, dx1, _f32(g1), eps, want)
-            # y1 = dropout1(att Wo^T + bo) + h
-            dy1 = dy1r if drop is None else ops.dropout_bf16(dy1r, drop["hidden"], s1)
-            datt = ops.gemm(dy1, _w16(ow.t()))
-            dqkv = _attn_bwd(_pack_of(m, datt.device), qkv, att, datt, B, Tp, H, ctx.valid,
-                             None if drop is None or drop["attention"] <= 0 else (drop["attention"], sa))
-            wqkv = torch.cat([qw, kw, vw], 0)
-            dh = ops.gemm(dqkv, _w16(wqkv.t()), residual=dy1r)                 # [M, d] = dqkv Wqkv + dy1 (unmasked: the residual path)
-            if want:
-                dwqkv = wgrad(dqkv, h)
-                dbqkv = ops.colsum_bf16(dqkv)
-                base = li * PER_LAYER
-                grads[base + 0], grads[base + 2], grads[base + 4] = dwqkv[:d], dwqkv[d:2 * d], dwqkv[2 * d:]
-                grads[base + 1], grads[base + 3], grads[base + 5] = dbqkv[:d], dbqkv[d:2 * d], dbqkv[2 * d:]
-                grads[base + 6], grads[base + 7] = wgrad(dy1, att), ops.colsum_bf16(dy1)
-                grads[base + 8], grads[base + 9] = dg1, db1n
-                grads[base + 10], grads[base + 11] = wgrad(du, x1), ops.colsum_bf16(du)
-                grads[base + 12], grads[base + 13] = wgrad(dy2, hm), ops.colsum_bf16(dy2)
-                grads[base + 14], grads[base + 15] = dg2, db2n
-            g = dh
+            g, pieces = layer(g, acts[7 * li:7 * li + 7], params[li * PER_LAYER:(li + 1) * PER_LAYER], ctx.pk, shape, ctx.valid, bool(train[li]), drop,
+                              m["seeds"][4 * li:4 * li + 4] if drop is not None else (0, 0, 0, 0))
+            if pieces is not None:
+                _param_grads(grads, li * PER_LAYER, *pieces)
             if li > 0:
                 ops.axpy_bf16(g, dhidden[li - 1], 1.0)                         # + the direct gradient of hidden[li - 1] (its share of the layer mix)
-        return (None, g if ctx.needs_input_grad[1] else None, None, *grads)
+        dh_in = None if not ctx.needs_input_grad[1] else g.float() if pre_ln else g
+        return (None, dh_in, None, *grads)
 
 
 class WeightedSumTrainFn(torch.autograd.Function):
