@@ -475,6 +475,23 @@ int64_t sc_attention_bwd_packed_workspace_bytes(int64_t total_rows, int H);
 int sc_attention_bwd_packed(const void* q, const void* k, const void* v, int64_t ld_qkv, const void* O, const void* dO, int64_t ld_o,
                             const int32_t* klens, const int32_t* row_off, int B, int H, int Tmax, int64_t total_rows, int head_dim, float scale,
                             float drop_p, uint32_t seed, void* dq, void* dk, void* dv, int64_t ld_dqkv, void* workspace, void* stream);
+
+/* ---- Fused attention backward for head_dim 64 / 96 / 128: the backward of sc_attention_hd_fwd, operands addressed exactly as there (all bf16; element
+ * (b, t, h, e) of q at b*q_bs + t*q_rs + h*head_dim + e, of k / v at b*kv_bs + ..., of O / dO (the forward's bf16 output and its gradient) at b*o_bs + ...,
+ * of dq at b*dq_bs + ..., of dk / dv at b*dkv_bs + ...; every stride a multiple of 8 elements).  Served: Tq == Tk (self-attention rows) and Tq == 1 (the
+ * CLS query of a branch's last layer); any other pair and any other head dim return an error.  The three-kernel structure of sc_attention_bwd_packed:
+ * `workspace` (sc_attention_hd_bwd_workspace_bytes: 2 fp32 per (b, h, query row)) receives log-sum-exp and delta = dO . O; a key-tile-stationary sweep
+ * gives dK / dV, a query-tile-stationary sweep dQ; fp32 scores / softmax / accumulators; nothing of size Tq x Tk is written; no atomics (bitwise reproducible).
+ * klens[b] is clamped to [0, Tk] (NULL = Tk).  Query row t takes part iff t < klens[b]: other query rows get dq = 0 and add nothing to dk / dv; key rows
+ * >= klens[b] get dk = dv = 0; every row of dq / dk / dv is written.  K / V rows >= klens[b] and Q / dO rows that take no part may hold anything (they are
+ * zeroed on load).  drop_p > 0: the forward ran with (drop_p, seed); its mask (pair index ((b*H + h)*Tk + t) * ceil(Tk / 2) + key / 2) is regenerated: P for
+ * dV is the dropped, rescaled one, dP is masked before the softmax backward (sc_attn_softmax_bwd_dropout's semantics).  B == 0 or Tk == 0: returns 0, no launch. */
+int64_t sc_attention_hd_bwd_workspace_bytes(int B, int H, int Tq);
+int sc_attention_hd_bwd(const void* q, const void* k, const void* v, const void* O, const void* dO, const int32_t* klens,
+                        int B, int H, int Tq, int Tk, int head_dim,
+                        int64_t q_bs, int64_t q_rs, int64_t kv_bs, int64_t kv_rs, int64_t o_bs, int64_t o_rs,
+                        void* dq, int64_t dq_bs, int64_t dq_rs, void* dk, void* dv, int64_t dkv_bs, int64_t dkv_rs,
+                        float scale, float drop_p, uint32_t seed, void* workspace, void* stream);
 #ifdef __cplusplus
 }
 #endif

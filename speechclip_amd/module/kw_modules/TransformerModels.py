@@ -212,6 +212,19 @@ class TransformerEncoder(nn.Module):
         x2 = ops.layernorm(y2, f32(L.norm2.weight), f32(L.norm2.bias), self.eps, out_f32=True)
         return ops.layernorm(x2, f32(self.model.norm.weight), f32(self.model.norm.bias), 1e-5)
 
+    def forward_cls_train(self, cls: torch.Tensor, audio_feat: torch.Tensor, audio_len: torch.Tensor, seed: int = None) -> torch.Tensor:
+        """The differentiable counterpart of `forward_cls` for the stack (n_layers >= 2 or norm_first): f32 [B, D] with gradients to `cls`,
+        `audio_feat` (when it requires one) and every parameter of `self.model`, as ONE autograd node (train_branch.BranchStackTrainFn).  Dropout
+        (rate `dropout` at the four sites of every layer) is active iff `self.training`; `seed` = None draws one from torch's generator."""
+        if not self.stacked:
+            raise NotImplementedError("forward_cls_train: the one-layer post-LN head trains through ParallelBranchTrainFn (its algebraic path)")
+        from ...train_branch import BranchStackTrainFn, stack_params
+        pd = float(self.model.layers[0].dropout.p) if self.training else 0.0
+        if pd > 0 and seed is None:
+            seed = int(torch.randint(0, 2 ** 31 - 1, (1,)).item())
+        meta = dict(heads=self.nhead, eps=self.eps, pre_ln=self.norm_first, drop_p=pd, seed=int(seed or 0))
+        return BranchStackTrainFn.apply(meta, cls, audio_feat.to(BF), audio_len, *stack_params(self.model))
+
     # ---- stack path (n_layers >= 2 or norm_first): layers 0..n-2 on every row of [CLS; frames] (padded [B, T + 1, d] rows, key lengths
     #      len + 1), then the last layer on the B CLS rows only: K / V of all rows, per-utterance CLS query.  Eval-mode arithmetic, no autograd.
     @torch.no_grad()

@@ -318,6 +318,43 @@ def attention_hd_qkv(qkv, B, L, H, klens_i32=None, out_f32=False, drop_p=0.0, se
     return out.view(B * L, D)
 
 
+def _attention_hd_bwd(q, k, v, O, dO, klens_i32, B, H, Tq, Tk, hd, q_strides, kv_strides, dq, dq_strides, dk, dv, dkv_strides, drop_p, seed):
+    """sc_attention_hd_bwd into caller-owned dq / dk / dv views (data_ptr = element (b 0, row 0, head 0)); O / dO bf16 contiguous [B, Tq, H*hd]."""
+    _need_cuda(q, k, v, O, dO, klens_i32)
+    D = H * hd
+    for t in (q, k, v, O, dO, dq, dk, dv):
+        assert t.dtype == bf16
+    assert O.is_contiguous() and dO.is_contiguous() and O.numel() == B * Tq * D and dO.numel() == B * Tq * D
+    ws = torch.empty(lib().sc_attention_hd_bwd_workspace_bytes(B, H, Tq), device=q.device, dtype=torch.uint8)
+    check(lib().sc_attention_hd_bwd(ptr(q), ptr(k), ptr(v), ptr(O), ptr(dO), ptr(klens_i32), B, H, Tq, Tk, hd, q_strides[0], q_strides[1], kv_strides[0],
+                                    kv_strides[1], Tq * D, D, ptr(dq), dq_strides[0], dq_strides[1], ptr(dk), ptr(dv), dkv_strides[0], dkv_strides[1],
+                                    hd ** -0.5, float(drop_p), int(seed) & 0xffffffff, ptr(ws), stream()), "sc_attention_hd_bwd")
+
+
+def attention_hd_bwd(q, k, v, O, dO, B, H, Tq, Tk, hd, q_strides, kv_strides, klens_i32=None, drop_p=0.0, seed=0):
+    """Backward of attention_hd (sc_attention_hd_bwd; Tq == Tk or Tq == 1, head_dim 64 / 96 / 128; anything else raises SpeechClipHipError).  q / k / v and
+    their strides as attention_hd took them; O / dO bf16 [B, Tq, H*hd]: the forward's bf16 output and its gradient; (drop_p, seed) of that forward.
+    Returns dq bf16 [B, Tq, D] and dk, dv: the two column halves of ONE bf16 [B, Tk, 2*D] buffer (dk | dv: what the k | v projection's backward consumes).
+    The only temporary is the fp32 statistics workspace (2 floats per (b, h, query row))."""
+    D = H * hd
+    dq = torch.empty(B, Tq, D, device=q.device, dtype=bf16)
+    dkv = torch.empty(B, Tk, 2 * D, device=q.device, dtype=bf16)
+    dk, dv = dkv[..., :D], dkv[..., D:]
+    _attention_hd_bwd(q, k, v, O, dO, klens_i32, B, H, Tq, Tk, hd, q_strides, kv_strides, dq, (Tq * D, D), dk, dv, (Tk * 2 * D, 2 * D), drop_p, seed)
+    return dq, dk, dv
+
+
+def attention_hd_qkv_bwd(qkv, att, datt, B, L, H, klens_i32=None, drop_p=0.0, seed=0):
+    """Backward of attention_hd_qkv: qkv bf16 [B*L, 3*D] (q | k | v), att / datt bf16 [B*L, D] (the forward's output and its gradient) -> dqkv bf16 [B*L, 3*D]."""
+    assert qkv.dim() == 2 and qkv.is_contiguous() and qkv.shape[0] == B * L and qkv.shape[1] % (3 * H) == 0
+    D = qkv.shape[1] // 3
+    assert att.shape == (B * L, D) and datt.shape == (B * L, D)
+    s = (L * 3 * D, 3 * D)
+    out = torch.empty(B * L, 3 * D, device=qkv.device, dtype=bf16)
+    _attention_hd_bwd(qkv, qkv[:, D:], qkv[:, 2 * D:], att, datt, klens_i32, B, H, L, L, D // H, s, s, out, s, out[:, D:], out[:, 2 * D:], s, drop_p, seed)
+    return out
+
+
 def attention_rows(qkv, B, L, H, hd, key_padding_mask=None, scale=None):
     """Full-row MHA for any head dim: qkv bf16 [B*L, 3*H*hd] packed (q|k|v); key_padding_mask bool/uint8 [B, L] (True = padding) or None.
     Returns bf16 [B*L, H*hd] (heads concatenated, before out_proj)."""

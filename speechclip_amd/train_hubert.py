@@ -136,6 +136,9 @@ def _attn_bwd(pk, qkv, att, datt, B, Tp, H, valid_i32, drop=None):
     return attention_bwd(qkv, att, datt, B, Tp, H, valid_i32, drop)
 
 
+ATTN_HUBERT = (_attn_fwd, _attn_bwd)     # the layer bodies' default attention pair (head_dim 64); train_branch.py passes the head_dim 64 / 96 / 128 pair
+
+
 def _site_seeds(seed, count):
     """`count` dropout-site seeds from one forward's seed, in forward order (the LCG of the frozen forward's next_seed)."""
     s0, seeds = int(seed) & 0x7fffffff, []
@@ -146,23 +149,25 @@ def _site_seeds(seed, count):
 
 
 # One layer, forward: (h, the converted q|k|v weight and bias, the layer's other 10 parameters, pk, (B, Tp, H, eps), valid_i32, out = hidden[li],
-# drop, this layer's 4 site seeds) -> the 7 tensors its backward reads; the layer's output is written into `out`.
+# drop, this layer's 4 site seeds, attn = the (forward, backward) attention pair, None = ATTN_HUBERT) -> the 7 tensors its backward reads; the layer's
+# output is written into `out`.
 
-def _layer_fwd_post_ln(h, wqkv, bqkv, p, pk, shape, valid_i32, out, drop, seeds):
+def _layer_fwd_post_ln(h, wqkv, bqkv, p, pk, shape, valid_i32, out, drop, seeds, attn=None):
     B, Tp, H, eps = shape
     M, d = h.shape
     ow, ob, g1, b1n, w1, b1, w2, b2, g2, b2n = p
+    attn_fwd = (attn or ATTN_HUBERT)[0]
     qkv = _qkv_rows(pk, M, Tp, d, h.device)
     ops.gemm(h, wqkv, bqkv, out=qkv[:M])
     if drop is None:
-        att = _attn_fwd(pk, qkv, M, B, Tp, H, valid_i32)
+        att = attn_fwd(pk, qkv, M, B, Tp, H, valid_i32)
         y1 = ops.gemm(att, _w16(ow), _f32(ob), residual=h)
         x1 = ops.layernorm(y1, _f32(g1), _f32(b1n), eps)
         hm = ops.gemm(x1, _w16(w1), _f32(b1), ACT_GELU)
         y2 = ops.gemm(hm, _w16(w2), _f32(b2), residual=x1)
     else:       # x = LN(x + dropout1(attn(x)));  x = LN(x + dropout3(fc2(dropout2(gelu(fc1 x)))))
         sa, s1, s2, s3 = seeds
-        att = _attn_fwd(pk, qkv, M, B, Tp, H, valid_i32, (drop["attention"], sa))
+        att = attn_fwd(pk, qkv, M, B, Tp, H, valid_i32, (drop["attention"], sa))
         y1 = ops.gemm(att, _w16(ow), _f32(ob))
         ops.dropout_bf16(y1, drop["hidden"], s1, residual=h, out=y1)
         x1 = ops.layernorm(y1, _f32(g1), _f32(b1n), eps)
@@ -175,27 +180,43 @@ def _layer_fwd_post_ln(h, wqkv, bqkv, p, pk, shape, valid_i32, out, drop, seeds)
     return [h, qkv, att, y1, x1, hm, y2]
 
 
-def _layer_fwd_pre_ln(h, wqkv, bqkv, p, pk, shape, valid_i32, out, drop, seeds):
+def _layer_fwd_pre_ln(h, wqkv, bqkv, p, pk, shape, valid_i32, out, drop, seeds, attn=None):
     """Pre-LN layers ([3P fairseq] layer_norm_first, HuBERT-large): x += attn(LN1 x); x += fc2(gelu(fc1(LN2 x))) on an fp32 residual stream.
-    h / out are f32; the saved copies of the stream (LayerNorm inputs of the backward) are bf16.  The large checkpoint's dropouts are 0."""
+    h / out are f32; the saved copies of the stream (LayerNorm inputs of the backward) are bf16.  The large checkpoint's dropouts are 0, so
+    HuBERT passes drop = None; with `drop` (the parallel branch, train_branch.py) each bf16 branch output is dropped before its fp32 residual add."""
     B, Tp, H, eps = shape
     M, d = h.shape
     ow, ob, g1, b1n, w1, b1, w2, b2, g2, b2n = p
     t1 = ops.layernorm(h, _f32(g1), _f32(b1n), eps)                                   # bf16
     qkv = _qkv_rows(pk, M, Tp, d, h.device)
     ops.gemm(t1, wqkv, bqkv, out=qkv[:M])
-    att = _attn_fwd(pk, qkv, M, B, Tp, H, valid_i32)
-    xmid = ops.gemm(att, _w16(ow), _f32(ob), residual=h, out_f32=True)
-    t2 = ops.layernorm(xmid, _f32(g2), _f32(b2n), eps)
-    hm = ops.gemm(t2, _w16(w1), _f32(b1), ACT_GELU)
-    ops.gemm(hm, _w16(w2), _f32(b2), residual=xmid, out=out, out_f32=True)
+    attn_fwd = (attn or ATTN_HUBERT)[0]
+    if drop is None:
+        att = attn_fwd(pk, qkv, M, B, Tp, H, valid_i32)
+        xmid = ops.gemm(att, _w16(ow), _f32(ob), residual=h, out_f32=True)
+        t2 = ops.layernorm(xmid, _f32(g2), _f32(b2n), eps)
+        hm = ops.gemm(t2, _w16(w1), _f32(b1), ACT_GELU)
+        ops.gemm(hm, _w16(w2), _f32(b2), residual=xmid, out=out, out_f32=True)
+    else:       # x += dropout1(attn(LN1 x));  x += dropout3(fc2(dropout2(gelu(fc1(LN2 x)))))
+        sa, s1, s2, s3 = seeds
+        att = attn_fwd(pk, qkv, M, B, Tp, H, valid_i32, (drop["attention"], sa))
+        o = ops.gemm(att, _w16(ow), _f32(ob))
+        ops.dropout_bf16(o, drop["hidden"], s1, out=o)
+        xmid = h + o.float()
+        t2 = ops.layernorm(xmid, _f32(g2), _f32(b2n), eps)
+        hm = ops.gemm(t2, _w16(w1), _f32(b1), ACT_GELU)
+        if drop["activation"] > 0:
+            ops.dropout_bf16(hm, drop["activation"], s2, out=hm)
+        f = ops.gemm(hm, _w16(w2), _f32(b2))
+        ops.dropout_bf16(f, drop["hidden"], s3, out=f)
+        torch.add(xmid, f.float(), out=out)
     return [h.to(BF), qkv, att, xmid.to(BF), t1, hm, t2]
 
 
 # One layer, backward: (g = gradient of the layer's output (bf16), its 7 saved tensors, its 16 parameters, pk, (B, Tp, H, eps), valid_i32, want, drop,
 # its 4 site seeds) -> (dh, the operands of the layer's parameter gradients in `_param_grads` order, or None without `want`).
 
-def _layer_bwd_post_ln(g, acts, p, pk, shape, valid_i32, want, drop, seeds):
+def _layer_bwd_post_ln(g, acts, p, pk, shape, valid_i32, want, drop, seeds, attn=None):
     B, Tp, H, eps = shape
     h, qkv, att, y1, x1, hm, y2 = acts
     qw, qb, kw, kb, vw, vb, ow, ob, g1, b1n, w1, b1, w2, b2, g2, b2n = p
@@ -217,32 +238,37 @@ def _layer_bwd_post_ln(g, acts, p, pk, shape, valid_i32, want, drop, seeds):
     # y1 = dropout1(att Wo^T + bo) + h
     dy1 = dy1r if drop is None else ops.dropout_bf16(dy1r, drop["hidden"], s1)
     datt = ops.gemm(dy1, _w16(ow.t()))
-    dqkv = _attn_bwd(pk, qkv, att, datt, B, Tp, H, valid_i32, None if drop is None or drop["attention"] <= 0 else (drop["attention"], sa))
+    dqkv = (attn or ATTN_HUBERT)[1](pk, qkv, att, datt, B, Tp, H, valid_i32, None if drop is None or drop["attention"] <= 0 else (drop["attention"], sa))
     wqkv = torch.cat([qw, kw, vw], 0)
     dh = ops.gemm(dqkv, _w16(wqkv.t()), residual=dy1r)                 # [M, d] = dqkv Wqkv + dy1 (unmasked: the residual path)
     return dh, (dqkv, h, dy1, att, du, x1, dy2, hm, dg1, db1n, dg2, db2n) if want else None
 
 
-def _layer_bwd_pre_ln(g, acts, p, pk, shape, valid_i32, want, drop, seeds):
+def _layer_bwd_pre_ln(g, acts, p, pk, shape, valid_i32, want, drop, seeds, attn=None):
     B, Tp, H, eps = shape
     h16, qkv, att, xmid16, t1, hm, t2 = acts
     qw, qb, kw, kb, vw, vb, ow, ob, g1, b1n, w1, b1, w2, b2, g2, b2n = p
-    # out = xmid + fc2(gelu(fc1(t2))),  t2 = LN2(xmid)
-    dhm = ops.gemm(g, _w16(w2.t()))
+    sa, s1, s2, s3 = seeds
+    # out = xmid + dropout3(fc2(dropout2(gelu(fc1(t2))))),  t2 = LN2(xmid): the residual path takes g as it is, the fc2 branch the masked gradient
+    dy2 = g if drop is None else ops.dropout_bf16(g, drop["hidden"], s3)
+    dhm = ops.gemm(dy2, _w16(w2.t()))
+    if drop is not None and drop["activation"] > 0:
+        ops.dropout_bf16(dhm, drop["activation"], s2, out=dhm)
     u = ops.gemm(t2, _w16(w1), _f32(b1))
     du = ops.gelu_bwd_bf16(u, dhm)
     del u, dhm
     dt2 = ops.gemm(du, _w16(w1.t()))
     dxm, dg2, db2n = ops.layernorm_bwd_bf16(xmid16, dt2, _f32(g2), eps, want)
     ops.axpy_bf16(dxm, g, 1.0)                                 # + the residual path
-    # xmid = h + out_proj(attn(qkv(t1))),  t1 = LN1(h)
-    datt = ops.gemm(dxm, _w16(ow.t()))
-    dqkv = _attn_bwd(pk, qkv, att, datt, B, Tp, H, valid_i32)
+    # xmid = h + dropout1(out_proj(attn(qkv(t1)))),  t1 = LN1(h)
+    dy1 = dxm if drop is None else ops.dropout_bf16(dxm, drop["hidden"], s1)
+    datt = ops.gemm(dy1, _w16(ow.t()))
+    dqkv = (attn or ATTN_HUBERT)[1](pk, qkv, att, datt, B, Tp, H, valid_i32, None if drop is None or drop["attention"] <= 0 else (drop["attention"], sa))
     wqkv = torch.cat([qw, kw, vw], 0)
     dt1 = ops.gemm(dqkv, _w16(wqkv.t()))
     dh, dg1, db1n = ops.layernorm_bwd_bf16(h16, dt1, _f32(g1), eps, want)
     ops.axpy_bf16(dh, dxm, 1.0)
-    return dh, (dqkv, t1, dxm, att, du, t2, g, hm, dg1, db1n, dg2, db2n) if want else None
+    return dh, (dqkv, t1, dy1, att, du, t2, dy2, hm, dg1, db1n, dg2, db2n) if want else None
 
 
 def _param_grads(grads, base, dqkv, x_qkv, dyo, att, du, x_fc1, dy2, hm, dg1, db1n, dg2, db2n):
