@@ -328,6 +328,36 @@ int sc_attn_small_bwd(const void* qkv, const float* dout, float* dqkv, int B, in
 int sc_quickgelu_f32(const float* z, void* y_or_dh, int64_t n, int backward, int out_bf16, void* stream);
 int sc_vq_st_bwd(const float* cos_scores, float* dprob_inout, float* rowdot, int R, int V, float temp, const int* mask_ids, int n_mask, void* stream);
 int sc_cosine_bwd_finish(const float* a, const float* G, const float* rowdot, float* da, int R, int E, float eps, void* stream);
+/* SimpleVectorQuantizer, the modes beside the shipped one (my_vector_quantizer.py:124-139 in train mode; csrc/vq_modes.hip):
+ *   y = softmax((x + g) / T) over the unmasked sub-words, x = scores f32 [R,V], g = Gumbel noise (use_gumbel) or 0, masked columns: probability and gradient 0.
+ *   soft (hard: false): subword_prob = y, keywords = y @ emb; gumbel hard: subword_prob = one-hot(arg-max(x + g)), gradient through y; gumbel soft: both from y.
+ * NOISE CONTRACT (part of the ABI: the backward and any host restatement regenerate it): idx = r * V + v as uint32 (R * V >= 2^32 is refused),
+ *   h = hash32(seed ^ hash32(idx + 0x9e3779b9)) with hash32(x): x ^= x >> 16; x *= 0x7feb352d; x ^= x >> 15; x *= 0x846ca68b; x ^= x >> 16 (the dropout hash),
+ *   u = ((h >> 9) + 0.5) * 2^-23 (exact in fp32, in [2^-24, 1 - 2^-24]), e = -log u (the Exponential(1) draw of F.gumbel_softmax), g = -log e in [-2.82, 16.64];
+ *   both logarithms are the accurate logf.  Every entry: seed_on = 0 means g = 0 (seed ignored); mask ids as in sc_vq_st_bwd (at most 8); no atomics, results
+ *   bitwise identical run to run.
+ * sc_vq_gumbel_noise: out f32 [R,V] = g.
+ * sc_vq_noisy_argmax: targets[r] = arg-max_v (x + g) over the unmasked sub-words, the lowest index on ties.
+ * sc_vq_probs: out f32 [R,V] = y (dense; for the lazy `subword_prob` and for shapes sc_vq_soft_embed does not cover).
+ * sc_vq_soft_table: the sub-word table emb f32 [V,E] (E % 64 == 0) as the bf16 (hi, lo) B operand of v_mfma_f32_16x16x32_bf16, sc_vq_soft_table_bytes(V, E) bytes:
+ *   table[half][vb][et][lane][j] = half(emb[32 vb + 8 (lane >> 4) + j][16 et + (lane & 15)]), hi = bf16(emb), lo = bf16(emb - hi), rows beyond V zero.
+ * sc_vq_soft_embed: keywords f32 [R,E] = y @ emb without an [R,V] image of y: a pre-pass writes row_max[r] = max_v (x + g) and
+ *   row_den[r] = sum_v exp((x + g - row_max) / T); the main kernel forms 128 x 32 tiles of P = exp(..) / row_den, split (hi, lo), and accumulates
+ *   P_hi E_hi + P_lo E_hi + P_hi E_lo on the MFMA.  V is split over `nsplit` chunks (0 = auto: about one block per CU); P being normalised, the partial products
+ *   [nsplit, R, E] in `workspace` (sc_vq_soft_embed_workspace_bytes; none for one chunk) add in a fixed order.  Returns 1 without a launch ("not covered")
+ *   unless E % 64 == 0 and V >= 5.
+ * sc_vq_mode_bwd: dprob_inout f32 [R,V] (d loss / d y) -> d loss / d cos = y (dprob - sum y dprob) / T in place; rowdot_cos[r] = sum_v dcos cos (for
+ *   sc_cosine_bwd_finish), rowdot_z[r] = sum_v dcos (cos + g): d loss / d T = -(1 / T) sum_r rowdot_z[r].  With seed_on = 0 it returns sc_vq_st_bwd's bits. */
+int sc_vq_gumbel_noise(float* out, int R, int V, uint32_t seed, void* stream);
+int sc_vq_noisy_argmax(const float* scores, int64_t* targets, int R, int V, uint32_t seed, int seed_on, const int* mask_ids, int n_mask, void* stream);
+int sc_vq_probs(const float* scores, float* out, int R, int V, float temp, uint32_t seed, int seed_on, const int* mask_ids, int n_mask, void* stream);
+int64_t sc_vq_soft_table_bytes(int V, int E);
+int sc_vq_soft_table(const float* emb, void* table, int V, int E, void* stream);
+int64_t sc_vq_soft_embed_workspace_bytes(int R, int V, int E, int nsplit);
+int sc_vq_soft_embed(const float* scores, const void* table, float* keywords, float* row_max, float* row_den, void* workspace, int R, int V, int E,
+                     float temp, uint32_t seed, int seed_on, const int* mask_ids, int n_mask, int nsplit, void* stream);
+int sc_vq_mode_bwd(const float* cos_scores, float* dprob_inout, float* rowdot_cos, float* rowdot_z, int R, int V, float temp, uint32_t seed, int seed_on,
+                   const int* mask_ids, int n_mask, void* stream);
 int sc_kw_bn_train_fwd(const float* x, const float* gamma, const float* beta, float* y, float* mean_out, float* rstd_out, float* running_mean,
                        float* running_var, int B, int K, int E, float momentum, float eps, void* stream);
 int sc_kw_bn_bwd(const float* x, const float* dy, const float* gamma, const float* mean, const float* rstd, float* dx, float* dgamma, float* dbeta,

@@ -142,6 +142,14 @@ def _declare(L):
         "sc_quickgelu_f32": ([P, P, L64, I, I, P], c_int),
         "sc_vq_st_bwd": ([P, P, P, I, I, F, P, I, P], c_int),
         "sc_cosine_bwd_finish": ([P, P, P, P, I, I, F, P], c_int),
+        "sc_vq_gumbel_noise": ([P, I, I, U32, P], c_int),
+        "sc_vq_noisy_argmax": ([P, P, I, I, U32, I, P, I, P], c_int),
+        "sc_vq_probs": ([P, P, I, I, F, U32, I, P, I, P], c_int),
+        "sc_vq_soft_table_bytes": ([I, I], c_int64),
+        "sc_vq_soft_table": ([P, P, I, I, P], c_int),
+        "sc_vq_soft_embed_workspace_bytes": ([I, I, I, I], c_int64),
+        "sc_vq_soft_embed": ([P, P, P, P, P, P, I, I, I, F, U32, I, P, I, I, P], c_int),
+        "sc_vq_mode_bwd": ([P, P, P, P, I, I, F, U32, I, P, I, P], c_int),
         "sc_kw_bn_train_fwd": ([P, P, P, P, P, P, P, P, I, I, I, F, F, P], c_int),
         "sc_kw_bn_bwd": ([P, P, P, P, P, P, P, P, I, I, I, P], c_int),
         "sc_colsum": ([P, L64, I, I, P, I, P], c_int),

@@ -437,7 +437,8 @@ class KW_CascadedBranch(nn.Module):
 
 def _kw_cascaded_forward_train(self, audio_feat: torch.Tensor, audio_len: torch.Tensor):
     """Differentiable train-mode path (kwClip.py:868-916 under loss.backward()): train_tail.CascadedPoolTrainFn -> Kw_BatchNorm (batch
-    statistics) -> cosine / straight-through VQ (KeywordSTFn) -> frozen CLIP text tower with input gradients (TextTowerTrainFn)."""
+    statistics) -> cosine / straight-through VQ (KeywordSTFn; the quantizer's soft / gumbel modes: KeywordVQFn) -> frozen CLIP text tower with
+    input gradients (TextTowerTrainFn)."""
     from ..train_tail import CascadedPoolTrainFn, KeywordSTFn
     if isinstance(self.linear_proj, MLPLayers):
         raise NotImplementedError("training with a kw_projection MLP is not built (no shipped config has one); the eval forward is")
@@ -461,6 +462,13 @@ def _kw_cascaded_forward_train(self, audio_feat: torch.Tensor, audio_len: torch.
     vq_results = self.vector_quantizer(x=cos.view(B, K, emb.shape[0]))
     vq = self.vector_quantizer      # a learnable temperature (vq.temp: "learnable=...") goes in as the parameter itself: KeywordSTFn returns its gradient
     temp = vq.curr_temp if getattr(vq, "temp_type", "") == "learnable" else vq.temperature_value()
+    mode = dict.get(vq_results, "vq_mode")       # set by the quantizer's soft / gumbel train modes: (soft, scores, mask ids)
+    if mode is not None:
+        from ..train_tail import KeywordVQFn
+        keywords = KeywordVQFn.apply(kw.reshape(B * K, self.text_dim), cos, vq_results["targets"].reshape(-1), emb, temp, (0, 2, 3), mode[0],
+                                     vq_results["gumbel_seed"]).view(B, K, emb.shape[1])
+        feat = self.clip.encode_keywords(keywords, K)
+        return feat, vq_results, keywords
     keywords = KeywordSTFn.apply(kw.reshape(B * K, self.text_dim), cos, vq_results["targets"].reshape(-1), emb, temp, (0, 2, 3)).view(B, K, emb.shape[1])
     feat = self.clip.encode_keywords(keywords, K)
     return feat, vq_results, keywords

@@ -944,6 +944,123 @@ def vq_st_bwd_(cos, dprob, temp, mask_ids=(0, 2, 3)):
     return rowdot
 
 
+# ---- vector-quantizer modes beside the shipped one: soft / gumbel (vq_modes.hip; noise contract: include/speechclip_hip.h) ----
+def _mask_arg(mask_ids):
+    import ctypes
+    ids = (ctypes.c_int32 * max(1, len(mask_ids)))(*[int(i) for i in mask_ids])
+    return ids, ctypes.cast(ids, ctypes.c_void_p), len(mask_ids)
+
+
+def _seed_arg(seed):
+    """seed None / 0 -> (0, off): the branch draws its seeds from [1, 2^31 - 8), so 0 is free to mean "no noise" in vq_results["gumbel_seed"]."""
+    return (0, 0) if not seed else (int(seed) & 0xffffffff, 1)
+
+
+def vq_gumbel_noise(R, V, seed, device="cuda"):
+    """f32 [R,V] Gumbel(0,1) noise of (seed, r * V + v): what the VQ kernels regenerate on the fly."""
+    out = torch.empty(R, V, device=device, dtype=torch.float32)
+    check(lib().sc_vq_gumbel_noise(ptr(out), R, V, int(seed) & 0xffffffff, stream()), "sc_vq_gumbel_noise")
+    return out
+
+
+def vq_noisy_argmax(scores, seed=None, mask_ids=(0, 2, 3)):
+    """scores f32 [R,V] -> i64 [R] arg-max of scores + noise over the unmasked columns (lowest index on ties)."""
+    _f32c(scores)
+    R, V = scores.shape
+    targets = torch.empty(R, device=scores.device, dtype=torch.int64)
+    keep, ids, n = _mask_arg(mask_ids)
+    sd, on = _seed_arg(seed)
+    check(lib().sc_vq_noisy_argmax(ptr(scores), ptr(targets), R, V, sd, on, ids, n, stream()), "sc_vq_noisy_argmax")
+    return targets
+
+
+def vq_probs(scores, temp, seed=None, mask_ids=(0, 2, 3)):
+    """scores f32 [R,V] -> f32 [R,V] softmax((scores + noise) / temp) over the unmasked columns (masked: exactly 0)."""
+    _f32c(scores)
+    R, V = scores.shape
+    out = torch.empty(R, V, device=scores.device, dtype=torch.float32)
+    keep, ids, n = _mask_arg(mask_ids)
+    sd, on = _seed_arg(seed)
+    check(lib().sc_vq_probs(ptr(scores), ptr(out), R, V, float(temp), sd, on, ids, n, stream()), "sc_vq_probs")
+    return out
+
+
+_VQ_SOFT_TABLES = {}
+
+
+def vq_soft_table(emb):
+    """The frozen sub-word table as sc_vq_soft_embed's (hi, lo) bf16 MFMA operand, cached per table version like _cos_table."""
+    import weakref
+    key = emb.data_ptr()
+    hit = _VQ_SOFT_TABLES.get(key)
+    if hit is not None and hit[0] == (emb._version, param_epoch(emb), tuple(emb.shape)) and hit[2]() is emb:
+        return hit[1]
+    e = emb.detach().float().contiguous()
+    V, E = e.shape
+    tab = torch.empty(lib().sc_vq_soft_table_bytes(V, E), device=e.device, dtype=torch.uint8)
+    check(lib().sc_vq_soft_table(ptr(e), ptr(tab), V, E, stream()), "sc_vq_soft_table")
+    _VQ_SOFT_TABLES.clear()
+    _VQ_SOFT_TABLES[key] = ((emb._version, param_epoch(emb), tuple(emb.shape)), tab, weakref.ref(emb))
+    return tab
+
+
+# route of the soft modes' product: "fused" = sc_vq_soft_embed, "probs" = sc_vq_probs + a GEMM.  Fused won 3 of 3 interleaved pairs at V = 8112 and 49408
+# (profiles/vq_soft_embed_bench.txt); the tests run both.
+VQ_SOFT_ROUTE = "fused"
+
+
+def vq_soft_embed_probs(scores, emb, temp, seed=None, mask_ids=(0, 2, 3)):
+    """The composed route: y as a dense image (sc_vq_probs), then y @ emb -- on the MFMA GEMM with y and emb^T split into bf16 (hi, lo) terms where the GEMM
+    takes the shape (the three products hi.hi + lo.hi + hi.lo in one depth-3V call), on the fp32 SIMT sgemm otherwise."""
+    y = vq_probs(scores, temp, seed, mask_ids)
+    e = emb.detach().float().contiguous()
+    V, E = e.shape
+    if V % 64 == 0 and E % 4 == 0:
+        et = e.t().contiguous()
+        hi = et.to(bf16)
+        lo = (et - hi.float()).to(bf16)
+        return gemm(split_hilo(y, nblk=3), torch.cat([hi, hi, lo], dim=1).contiguous(), out_f32=True)
+    return sgemm(y, e)
+
+
+def vq_soft_embed(scores, emb, temp, seed=None, mask_ids=(0, 2, 3), nsplit=0, want_stats=False):
+    """keywords f32 [R,E] = softmax((scores + noise) / temp) @ emb, fused (no [R,V] probability image); `nsplit` chunks of V (0 = auto).
+    Shapes the fused kernel does not cover (E % 64, V < 5: it says so by returning 1) are composed from sc_vq_probs and a GEMM.
+    want_stats: also (row_max, row_den) f32 [R] of the fused kernel's pre-pass (None on the composed route)."""
+    _f32c(scores)
+    R, V = scores.shape
+    E = emb.shape[1]
+    assert emb.shape[0] == V, (emb.shape, V)
+    rc = 1
+    if VQ_SOFT_ROUTE == "fused":
+        tab = vq_soft_table(emb) if E % 64 == 0 and E >= 64 else None        # without a table the kernel answers "not covered" before it looks at it
+        kw = torch.empty(R, E, device=scores.device, dtype=torch.float32)
+        rmax = torch.empty(R, device=scores.device, dtype=torch.float32)
+        rden = torch.empty(R, device=scores.device, dtype=torch.float32)
+        ws = torch.empty(lib().sc_vq_soft_embed_workspace_bytes(R, V, E, int(nsplit)), device=scores.device, dtype=torch.uint8)
+        keep, ids, n = _mask_arg(mask_ids)
+        sd, on = _seed_arg(seed)
+        rc = lib().sc_vq_soft_embed(ptr(scores), ptr(tab), ptr(kw), ptr(rmax), ptr(rden), ptr(ws), R, V, E, float(temp), sd, on, ids, n, int(nsplit), stream())
+        if rc not in (0, 1):
+            check(rc, "sc_vq_soft_embed")
+    if rc == 1:
+        kw, rmax, rden = vq_soft_embed_probs(scores, emb, temp, seed, mask_ids), None, None
+    return (kw, rmax, rden) if want_stats else kw
+
+
+def vq_mode_bwd_(cos, dprob, temp, seed=None, mask_ids=(0, 2, 3)):
+    """dprob f32 [R,V] (d loss / d y, y = softmax((cos + noise) / temp)) becomes d loss / d cos in place;
+    returns (rowdot_cos, rowdot_z) f32 [R] = sum_v dcos cos, sum_v dcos (cos + noise)."""
+    _f32c(cos, dprob)
+    R, V = cos.shape
+    rd = torch.empty(R, device=cos.device, dtype=torch.float32)
+    rz = torch.empty(R, device=cos.device, dtype=torch.float32)
+    keep, ids, n = _mask_arg(mask_ids)
+    sd, on = _seed_arg(seed)
+    check(lib().sc_vq_mode_bwd(ptr(cos), ptr(dprob), ptr(rd), ptr(rz), R, V, float(temp), sd, on, ids, n, stream()), "sc_vq_mode_bwd")
+    return rd, rz
+
+
 def cosine_bwd_finish(a, G, rowdot, eps=1e-8):
     _f32c(a, G, rowdot)
     da = torch.empty_like(a)

@@ -12,6 +12,7 @@ parameters the reference optimises and any torch optimizer -- or `FusedAdam` bel
   CascadedPoolTrainFn   : hidden states -> layer mix -> K keyword queries over [CLS_1..K; frames] -> LN(MHA + CLS) -> Linear          [B*K, E_txt]
   KwBatchNormTrainFn    : train-mode keyword BatchNorm (batch statistics, running-stat update)     (kw_bn.py:122-131)
   KeywordSTFn           : cosine scores -> straight-through VQ -> sub-word embeddings              (kwClip.py:889-911)
+  KeywordVQFn           : the same for the quantizer's soft / gumbel modes (fused softmax @ table) (my_vector_quantizer.py:124-131)
   TextTowerTrainFn      : frozen CLIP text tower with the gradient w.r.t. its input embeddings     (clip_official.py:220-264)
   L2NormFn              : x / |x|                                                      (kwClip.py:1436)
   MaskedContrastiveFn   : masked InfoNCE on the gathered global batch                  (losses.py:185-245)
@@ -348,6 +349,70 @@ class KeywordSTFn(torch.autograd.Function):
         G = _mfma_f32(dprob, U2)                                                              # dcos @ (emb / |emb|)  [R, E]
         dtemp = (rowdot.sum() * (-1.0 / ctx.temp)).reshape(1) if ctx.temp_is_param else None
         return ops.cosine_bwd_finish(kb, G, rowdot), None, None, None, dtemp, None
+
+
+_VQ_TABLES3 = {}
+
+
+def _vq_tables3(emb):
+    """Three-term operands of the quantizer-mode backward for the frozen sub-word table, cached like _vq_tables: (hi | hi | lo) bf16 of emb [V, 3E] and of
+    (emb/|emb|)^T [E, 3V].  Against an activation split (hi | lo | hi) one GEMM returns a_hi.w_hi + a_lo.w_hi + a_hi.w_lo: the soft modes' gradient flows
+    through every sub-word, not one row, so the table's own bf16 rounding (0.2 % per entry, what _vq_tables carries) would be a 1e-3 error of d loss / d a."""
+    import weakref
+    key = emb.data_ptr()
+    hit = _VQ_TABLES3.get(key)
+    if hit is not None and hit[0] == (emb._version, ops.param_epoch(emb), tuple(emb.shape)) and hit[2]() is emb:
+        return hit[1]
+
+    def three(w):
+        hi = w.to(BF)
+        return torch.cat([hi, hi, (w - hi.float()).to(BF)], dim=1).contiguous()
+
+    e = emb.detach().float().contiguous()
+    out = (three(e), three(ops.l2norm(e, clamp=True).t().contiguous()))
+    _VQ_TABLES3.clear()
+    _VQ_TABLES3[key] = ((emb._version, ops.param_epoch(emb), tuple(emb.shape)), out, weakref.ref(emb))
+    return out
+
+
+def _mfma3_f32(a: torch.Tensor, w3: torch.Tensor) -> torch.Tensor:
+    """f32 [M,N] = a f32 [M,K] @ W^T at fp32 grade on the MFMA GEMM, W given as w3 = (W_hi | W_hi | W_lo) bf16 [N, 3K]; shapes the GEMM kernel does
+    not take (3K % 64, N % 4: reduced test vocabularies) go to the fp32 SIMT sgemm with W_hi + W_lo."""
+    N, K3 = w3.shape
+    K = K3 // 3
+    if K3 % 64 or N % 4 or K % 4:
+        return ops.sgemm(a, (w3[:, :K].float() + w3[:, 2 * K:].float()).contiguous(), transb=True)
+    return ops.gemm(ops.split_hilo(a, nblk=3), w3, out_f32=True)
+
+
+class KeywordVQFn(torch.autograd.Function):
+    """keywords [R,E] = subword_prob @ emb for the quantizer's other train modes (my_vector_quantizer.py:124-131, kwClip.py:909-911) and the cosine
+    similarity behind them (kwClip.py:889-897), y = softmax((cos + g) / T) with g the Gumbel noise of `seed` (0: none):
+      soft         forward y @ emb (sc_vq_soft_embed), g = 0
+      gumbel soft  forward y @ emb (sc_vq_soft_embed)
+      gumbel hard  forward a gather of the noisy arg-max (F.gumbel_softmax(hard=True): y_hard - y.detach() + y)
+    The gradient flows through y in all three: dkw @ emb^T -> sc_vq_mode_bwd (noise regenerated from the seed) -> @ (emb/|emb|) -> sc_cosine_bwd_finish."""
+
+    @staticmethod
+    def forward(ctx, kb, cos, targets, emb, temp, mask_ids, soft, seed):
+        """temp: a float or the quantizer's learnable temperature parameter, as for KeywordSTFn; with z = (cos + g) / T its gradient is
+        d loss / d T = -(1 / T) sum_v dcos_v (cos_v + g_v), the `rowdot_z` of sc_vq_mode_bwd."""
+        ctx.save_for_backward(kb.detach().float().contiguous(), cos, emb)
+        ctx.temp_is_param = torch.is_tensor(temp) and temp.requires_grad
+        ctx.temp, ctx.mask_ids, ctx.seed = float(temp), tuple(int(i) for i in mask_ids), int(seed)
+        if soft:
+            return ops.vq_soft_embed(cos, emb, ctx.temp, ctx.seed, ctx.mask_ids)
+        return ops.gather_rows(emb, targets.reshape(-1))
+
+    @staticmethod
+    def backward(ctx, dkw):
+        kb, cos, emb = ctx.saved_tensors
+        E3, U3 = _vq_tables3(emb)
+        dprob = _mfma3_f32(dkw.float().contiguous(), E3)                                      # d loss / d y = dkw @ emb^T  [R, V]
+        rowdot, rowdot_z = ops.vq_mode_bwd_(cos, dprob, ctx.temp, ctx.seed, ctx.mask_ids)     # dprob is now d loss / d cos
+        G = _mfma3_f32(dprob, U3)                                                             # dcos @ (emb / |emb|)  [R, E]
+        dtemp = (rowdot_z.sum() * (-1.0 / ctx.temp)).reshape(1) if ctx.temp_is_param else None
+        return ops.cosine_bwd_finish(kb, G, rowdot), None, None, None, dtemp, None, None, None
 
 
 class TextTowerTrainFn(torch.autograd.Function):

@@ -6,7 +6,7 @@ import dataclasses
 
 def make_config(d_model=768, branch_heads=8, parallel=True, cascaded=False, hubert_name="hubert", clip_name="ViT-B/32",
                 hubert_config=None, clip_config=None, normalize_hiddenstates=False, temperature_trainable=False,
-                reduce_vocab=None, keyword_num=8):
+                reduce_vocab=None, keyword_num=8, vq_args=None):
     from ..base import OrderedNamespace
     targs = dict(n_layers=1, d_model=d_model, nhead=branch_heads, dim_feedforward=4 * d_model, dropout=0.1, activation="gelu",
                  layer_norm_eps=1e-5, batch_first=True, norm_first=False)
@@ -38,6 +38,8 @@ def make_config(d_model=768, branch_heads=8, parallel=True, cascaded=False, hube
         "trainer": {"max_steps": 50000, "gradient_clip_val": 4, "precision": 16},
         "log_setting": {"log_detokenize_results": False},
     }
+    if vq_args:      # the quantizer's unshipped switches (use_gumbel, hard, temp, groundTruthPerplexity): ablations of the cascaded model
+        cfg["model_settings"]["cascaded_branch"]["vq"]["args"].update(vq_args)
     if hubert_config is not None:
         cfg["audio_encoder"]["hubert_config"] = dataclasses.asdict(hubert_config)
     if clip_config is not None:
