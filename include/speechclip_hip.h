@@ -500,7 +500,8 @@ int sc_pack_rows(const void* src, int64_t src_layer_stride_bytes, const int32_t*
  * delta = dO . O of a pre-pass.  No atomics: results are bitwise reproducible.  drop_p > 0: the forward ran with (drop_p, seed); its mask is regenerated
  * (P for dV is the dropped, rescaled one, dP is masked before the softmax backward: sc_attn_softmax_bwd_dropout's semantics).
  * Query rows >= klens[b] of an utterance take no part: dq = 0 there and they add nothing to dk / dv; key rows >= klens[b] get dk = dv = 0.  Every row
- * in [0, total_rows) of dq / dk / dv is written. */
+ * in [0, total_rows) of dq / dk / dv is written.  Rows >= klens[b] of q / k / v, O and dO may hold anything, NaN and Inf included (they are zeroed on load).
+ * One kernel set (csrc/attention_bwd.hip) serves this entry and sc_attention_hd_bwd: at head_dim 64 on uniform rows without dropout the two return the same bits. */
 int64_t sc_attention_bwd_packed_workspace_bytes(int64_t total_rows, int H);
 int sc_attention_bwd_packed(const void* q, const void* k, const void* v, int64_t ld_qkv, const void* O, const void* dO, int64_t ld_o,
                             const int32_t* klens, const int32_t* row_off, int B, int H, int Tmax, int64_t total_rows, int head_dim, float scale,
@@ -509,8 +510,9 @@ int sc_attention_bwd_packed(const void* q, const void* k, const void* v, int64_t
 /* ---- Fused attention backward for head_dim 64 / 96 / 128: the backward of sc_attention_hd_fwd, operands addressed exactly as there (all bf16; element
  * (b, t, h, e) of q at b*q_bs + t*q_rs + h*head_dim + e, of k / v at b*kv_bs + ..., of O / dO (the forward's bf16 output and its gradient) at b*o_bs + ...,
  * of dq at b*dq_bs + ..., of dk / dv at b*dkv_bs + ...; every stride a multiple of 8 elements).  Served: Tq == Tk (self-attention rows) and Tq == 1 (the
- * CLS query of a branch's last layer); any other pair and any other head dim return an error.  The three-kernel structure of sc_attention_bwd_packed:
- * `workspace` (sc_attention_hd_bwd_workspace_bytes: 2 fp32 per (b, h, query row)) receives log-sum-exp and delta = dO . O; a key-tile-stationary sweep
+ * CLS query of a branch's last layer); any other pair and any other head dim return an error.  The kernel set of sc_attention_bwd_packed (one set, two entries):
+ * `workspace` (sc_attention_hd_bwd_workspace_bytes: 2 fp32 per (b, h, query row)) receives log-sum-exp and delta (dO . O; with drop_p > 0 the same number
+ * taken before O's rounding, sum_k P_dropped dP, which sc_attention_bwd_packed does not do); a key-tile-stationary sweep
  * gives dK / dV, a query-tile-stationary sweep dQ; fp32 scores / softmax / accumulators; nothing of size Tq x Tk is written; no atomics (bitwise reproducible).
  * klens[b] is clamped to [0, Tk] (NULL = Tk).  Query row t takes part iff t < klens[b]: other query rows get dq = 0 and add nothing to dk / dv; key rows
  * >= klens[b] get dk = dv = 0; every row of dq / dk / dv is written.  K / V rows >= klens[b] and Q / dO rows that take no part may hold anything (they are

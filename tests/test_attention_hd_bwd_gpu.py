@@ -210,7 +210,8 @@ def test_dropout_regenerates_the_forwards_mask(hd):
 
 
 def test_head_dim_64_beside_the_packed_kernel():
-    """The uniform layout through sc_attention_bwd_packed and through the new entry: both meet the fp64 bound (they round differently and are not compared)."""
+    """The uniform layout through sc_attention_bwd_packed and through sc_attention_hd_bwd: both meet the fp64 bound, and -- one kernel set behind both
+    entries, without dropout the same statistics kernel -- they return bitwise equal dqkv."""
     from speechclip_amd import ops
     hd, D = 64, H * 64
     qkv, dO = _full_inputs(hd, 64)
@@ -218,8 +219,11 @@ def test_head_dim_64_beside_the_packed_kernel():
     ref = _reference(q, k, v, dO.view(B, T, D), KLENS, H, hd)
     kl = _i32(KLENS)
     att = ops.attention_hd_qkv(qkv.cuda(), B, T, H, kl)
-    _check(_split(ops.attention_hd_qkv_bwd(qkv.cuda(), att, dO.cuda(), B, T, H, kl), B, T, D), ref, KLENS, "hd 64, sc_attention_hd_bwd")
-    _check(_split(ops.attention_bwd_packed(qkv.cuda(), att, dO.cuda(), B, T, H, kl, None), B, T, D), ref, KLENS, "hd 64, sc_attention_bwd_packed")
+    hd_out = ops.attention_hd_qkv_bwd(qkv.cuda(), att, dO.cuda(), B, T, H, kl)
+    packed_out = ops.attention_bwd_packed(qkv.cuda(), att, dO.cuda(), B, T, H, kl, None)
+    _check(_split(hd_out, B, T, D), ref, KLENS, "hd 64, sc_attention_hd_bwd")
+    _check(_split(packed_out, B, T, D), ref, KLENS, "hd 64, sc_attention_bwd_packed")
+    assert torch.equal(hd_out, packed_out)
 
 
 @pytest.mark.parametrize("drop", [(0.0, 0), (0.1, 77)])

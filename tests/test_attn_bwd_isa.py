@@ -1,7 +1,8 @@
-"""CPU-only checks of the fused attention backward's gfx950 code (csrc/attention_bwd.hip compiled with the Makefile's flags): both sweeps and the statistics
-pre-pass run on v_mfma_f32_16x16x32_bf16, use no scratch and spill nothing, contain no memory atomics (every output element has one writer: the
-determinism claim), and no packed fp32 add fed by two LDS-crossbar shuffles (the construct profiles/r06_vit_layernorm_nondeterminism.txt traced
-run-to-run differences to)."""
+"""CPU-only checks of the fused attention backward's gfx950 code (csrc/attention_bwd.hip, the one kernel set behind sc_attention_bwd_packed and
+sc_attention_hd_bwd, compiled with the Makefile's flags): every instantiation (head_dim 64 / 96 / 128; statistics, dK / dV and dQ sweeps, two forms each)
+runs on v_mfma_f32_16x16x32_bf16, uses no scratch and spills nothing, contains no memory atomics (every output element has one writer: the determinism
+claim), and no packed fp32 add fed by two LDS-crossbar shuffles (the construct profiles/r06_vit_layernorm_nondeterminism.txt traced run-to-run
+differences to)."""
 import os
 import re
 import subprocess
@@ -27,15 +28,22 @@ def bwd_asm(tmp_path_factory):
     subprocess.run([HIPCC, *flags, "--cuda-device-only", "-S", os.path.join(CSRC, "attention_bwd.hip"), "-o", str(out)], check=True, cwd=CSRC)
     text = out.read_text()
     kernels = {}
-    for m in re.finditer(r"^(_Z\w*attn_bwd_\w*kernel\w*):[^\n]*\n(.*?)^\s*s_endpgm", text, re.M | re.S):
-        kernels[m.group(1)] = m.group(2)
+    for m in re.finditer(r"^(_Z\w*attn_bwd_(?:stats|dq|dkv)_kernel\w*):[^\n]*\n(.*?)^\.Lfunc_end\d+:", text, re.M | re.S):
+        kernels[m.group(1)] = m.group(2)              # the whole body up to the function's end label: a kernel with early returns ends more than once
     return text, kernels
+
+
+def test_every_instantiation_is_there(bwd_asm):
+    _, kernels = bwd_asm
+    assert len(kernels) == 18, sorted(kernels)              # head_dim {64, 96, 128} x {stats, dkv, dq} x {delta source | dropout}
+    for kind in ("stats", "dkv", "dq"):
+        assert sum(f"attn_bwd_{kind}_kernel" in k for k in kernels) == 6, kind
+    for body in kernels.values():
+        assert "s_endpgm" in body
 
 
 def test_kernels_run_on_the_mfma_without_scratch_or_spills(bwd_asm):
     text, kernels = bwd_asm
-    assert len(kernels) == 5, sorted(kernels)               # statistics + (dQ sweep, dK/dV sweep) x dropout
-    assert sum("dq_kernel" in k for k in kernels) == 2 and sum("dkv_kernel" in k for k in kernels) == 2
     for name, body in kernels.items():
         assert "v_mfma_f32_16x16x32_bf16" in body, name
         assert "scratch_" not in body and "buffer_store" not in body, name
@@ -44,8 +52,24 @@ def test_kernels_run_on_the_mfma_without_scratch_or_spills(bwd_asm):
     assert not re.search(r"ScratchSize:\s*[1-9]", text)
     for key in ("vgpr_spill_count", "sgpr_spill_count"):
         vals = re.findall(rf"\.{key}:\s+(\d+)", text)
-        assert len(vals) == 5 and all(int(v) == 0 for v in vals), key
+        assert len(vals) == len(kernels) and all(int(v) == 0 for v in vals), key
     assert all(int(v) == 0 for v in re.findall(r"\.private_segment_fixed_size:\s+(\d+)", text))
+
+
+def test_no_scratch_and_no_spilled_registers(bwd_asm):
+    text, kernels = bwd_asm
+    for name, body in kernels.items():
+        assert "scratch_" not in body, name
+    assert not re.search(r"ScratchSize:\s*[1-9]", text)
+    spills = re.findall(r"\.vgpr_spill_count:\s+(\d+)", text)
+    assert len(spills) >= len(kernels) and all(int(v) == 0 for v in spills)
+    assert all(int(v) == 0 for v in re.findall(r"\.private_segment_fixed_size:\s+(\d+)", text))
+
+
+def test_scores_are_recomputed_on_the_bf16_16x16x32_mfma(bwd_asm):
+    _, kernels = bwd_asm
+    for name, body in kernels.items():
+        assert "v_mfma_f32_16x16x32_bf16" in body, name
 
 
 def test_kernels_have_no_memory_atomics(bwd_asm):

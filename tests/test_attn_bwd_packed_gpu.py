@@ -2,7 +2,8 @@
 
 The kernel is compared with torch autograd in fp64 on the CPU over the same bf16-rounded operands, per utterance: ragged row offsets (lengths 1, 63, 64,
 65 and a full Tmax among them), the uniform layout beside the existing image-based backward, the dropout form against the mask read back from the forward,
-run-to-run bitwise equality, and the memory it takes (no L x L image)."""
+the row_off and the uniform addressing of the same rows bit for bit, NaN on the rows that take no part, run-to-run bitwise equality, and the memory it
+takes (no L x L image)."""
 import pytest
 import torch
 import torch.nn.functional as F
@@ -109,6 +110,42 @@ def test_uniform_layout_beside_the_image_backward(B, T, H, lens):
         for c0 in (0, d, 2 * d):
             gv, rv = old[b * T:b * T + n, c0:c0 + d], ref[b * T:b * T + n, c0:c0 + d]
             assert _cos(gv, rv) > 0.999 and (gv - rv).abs().max().item() < 3e-2 * rv.abs().max().item() + 1e-3, ("image form", b, c0)
+
+
+def test_row_off_and_uniform_layouts_agree():
+    """Equal-length rows addressed through row_off and as the uniform layout (row_off = NULL) are the same units: without dropout the same bits.  (With
+    dropout the two layouts index the forward's mask differently by contract and are not compared.)"""
+    from speechclip_amd import ops
+    from speechclip_amd.train_hubert import attention_bwd_packed
+    rows, klens, H = [70, 70, 70], [70, 33, 64], 2
+    qkv, dO, off = _inputs(rows, H, 71)
+    assert off.tolist() == [0, 70, 140, 210]
+    kl = torch.tensor(klens, dtype=torch.int32).cuda()
+    att = ops.attention(qkv.cuda(), 3, 70, H, kl)
+    uniform = attention_bwd_packed(qkv.cuda(), att, dO.cuda(), 3, 70, H, kl, None)
+    packed = attention_bwd_packed(qkv.cuda(), att, dO.cuda(), 3, 70, H, kl, off.cuda())
+    assert torch.equal(packed, uniform) and bool(uniform.float().abs().sum() > 0)
+
+
+def test_rows_that_take_no_part_may_hold_anything():
+    """Rows >= klens[b] of every utterance (q | k | v, dO and the forward's output) are zeroed on load: NaN there changes no bit of the result, and every
+    row of it is finite.  att comes from the clean qkv: the packed forward still requires a finite V."""
+    from speechclip_amd import ops
+    from speechclip_amd.train_hubert import attention_bwd_packed
+    H = 2
+    qkv, dO, off = _inputs(ROWS, H, 9)
+    B, Tmax = len(ROWS), max(ROWS)
+    kl = torch.tensor(KLENS, dtype=torch.int32).cuda()
+    att = ops.attention_packed(qkv.cuda(), B, Tmax, H, kl, off.cuda())
+    clean = attention_bwd_packed(qkv.cuda(), att, dO.cuda(), B, Tmax, H, kl, off.cuda())
+    qkv2, dO2, att2 = qkv.clone(), dO.clone(), att.cpu().clone()
+    for b, k in enumerate(KLENS):
+        for x in (qkv2, dO2, att2):
+            x[int(off[b]) + k:int(off[b + 1])] = float("nan")
+    assert bool(torch.isnan(qkv2.float()).any()) and bool(torch.isnan(att2.float()).any())
+    got = attention_bwd_packed(qkv2.cuda(), att2.cuda(), dO2.cuda(), B, Tmax, H, kl, off.cuda())
+    assert bool(torch.isfinite(got.float()).all())
+    assert torch.equal(got, clean)
 
 
 def _recover_masks(qkv, rows, klens, H, off, drop_p, seed, packed):
