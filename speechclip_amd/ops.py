@@ -160,15 +160,21 @@ def layernorm(x, gamma, beta, eps=1e-5, out=None, out_f32=False, gelu=False, row
         shape = x.shape
     else:
         shape = (rows, D)
+    ld_out = D
     if out is None:
         out = torch.empty(shape, device=x.device, dtype=torch.float32 if out_f32 else bf16)
+    elif out.is_contiguous():
+        assert out.numel() == rows * D, (tuple(out.shape), rows, D)
+    else:                                    # a strided out: [rows, D] with its own row pitch
+        assert out.dim() == 2 and tuple(out.shape) == (rows, D) and out.stride(1) == 1, (tuple(out.shape), out.stride(), rows, D)
+        ld_out = out.stride(0)
     flags = (LN_IN_F32 if x.dtype == torch.float32 else 0) | (LN_OUT_F32 if out.dtype == torch.float32 else 0) | (LN_GELU if gelu else 0)
     if out.dtype == torch.float16:           # IEEE-half operand format of the pre-LN encoder layers (fp32 residual stream in)
         assert x.dtype == torch.float32
         flags |= LN_OUT_F16
     assert x.dtype in (bf16, torch.float32) and out.dtype in (bf16, torch.float16, torch.float32)
     with _HbmSpan("layernorm", rows * D * (x.element_size() + out.element_size())):
-        check(lib().sc_layernorm(ptr(x), ld_in, ptr(gamma), ptr(beta), ptr(out), D, rows, D, eps, flags, stream()), "sc_layernorm")
+        check(lib().sc_layernorm(ptr(x), ld_in, ptr(gamma), ptr(beta), ptr(out), ld_out, rows, D, eps, flags, stream()), "sc_layernorm")
     return out
 
 
