@@ -438,6 +438,22 @@ int sc_axpy_bf16(void* y, const void* x, float alpha, int64_t n, void* stream);
 int sc_cls_pool_dz(const float* pp, const float* ds, const float* dzbar, const float* u, const int32_t* lens, void* dz, int B, int T, int NQ, int R,
                    int D, int64_t ld_dz, void* stream);
 
+/* ---- Fine-tuning the CLIP image tower (clip_official.py `image_encoder_trainable`: model.visual trains).  The ViT blocks run on the pre-LN layer
+ * pieces above; these are the ViT-specific ones (train_vit.hip).
+ *   sc_quickgelu_bwd_bf16: du = dh (s + 1.702 u s (1 - s)), s = sigmoid(1.702 u): bf16 in / out, fp32 arithmetic.  Any n >= 0 and any 2-byte-aligned
+ *     operands; where u, dh and du share their address modulo 16 the body moves 16 bytes per lane.  du may be dh (in place).
+ *   sc_vit_embed_bwd: adjoint of sc_vit_embed, x0 = LN_pre([cls | patch] + pos).  dx f32 [B*ntok, D] = d loss / d x0; patch bf16 [B*(ntok-1), D], cls f32 [D],
+ *     pos f32 [ntok, D], gamma f32 [D]: the forward's inputs (the row, its mean and its rstd are recomputed; the forward saves nothing).  Outputs:
+ *     dpatch bf16 [B*(ntok-1), D] = gradient of the pre-LN rows of tokens >= 1 (the dY of the patch GEMM); dpos f32 [ntok, D] = the gradient of every pre-LN
+ *     row summed over the batch (row 0 is d loss / d cls); dgamma, dbeta f32 [D].  ntok >= 2, D % 4 == 0, D <= 1024; dx 16-byte, patch / dpatch 8-byte aligned
+ *     (cls, pos, gamma and the f32 outputs: any 4-byte alignment, e.g. views of an optimizer's flat buffer).  Reduction order (fixed, no atomics, bitwise reproducible): block (token, batch split) adds its batch entries wave by wave in
+ *     ascending order and writes one partial row triple into `workspace` (sc_vit_embed_bwd_workspace_bytes); the finish adds the splits in ascending
+ *     order for dpos and all (split, token) partials as four interleaved running sums for dgamma / dbeta. */
+int sc_quickgelu_bwd_bf16(const void* u, const void* dh, void* du, int64_t n, void* stream);
+int64_t sc_vit_embed_bwd_workspace_bytes(int B, int ntok, int D);
+int sc_vit_embed_bwd(const float* dx, const void* patch, const float* cls, const float* pos, const float* gamma, void* dpatch, float* dpos,
+                     float* dgamma, float* dbeta, float* workspace, int B, int ntok, int D, float eps, void* stream);
+
 
 /* ---- Padding-free (packed) batches.  The reference pads every utterance of a batch to the longest one (collate_function.py:18-30,
  * speech_encoder_plus.py:506-518, :540-556) and runs the conv stack and all transformer GEMMs on B x T_max rows; only rows below each

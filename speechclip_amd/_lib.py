@@ -114,6 +114,9 @@ def _declare(L):
         "sc_attention_bwd_packed": ([P, P, P, L64, P, P, L64, P, P, I, I, I, L64, I, F, F, U32, P, P, P, L64, P, P], c_int),
         "sc_attention_hd_bwd_workspace_bytes": ([I, I, I], c_int64),
         "sc_attention_hd_bwd": ([P, P, P, P, P, P, I, I, I, I, I, L64, L64, L64, L64, L64, L64, P, L64, L64, P, P, L64, L64, F, F, U32, P, P], c_int),
+        "sc_quickgelu_bwd_bf16": ([P, P, P, L64, P], c_int),
+        "sc_vit_embed_bwd_workspace_bytes": ([I, I, I], c_int64),
+        "sc_vit_embed_bwd": ([P, P, P, P, P, P, P, P, P, P, I, I, I, F, P], c_int),
         "sc_image_normalize_u8": ([P, P, I, I, I, P, P, P], c_int),
         "sc_vit_patchify": ([P, P, I, I, I, I, P], c_int),
         "sc_vit_embed": ([P, P, P, P, P, P, I, I, I, F, P], c_int),

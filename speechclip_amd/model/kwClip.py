@@ -577,7 +577,10 @@ class KWClip_GeneralTransformer(KWClipBase):
         wav, wav_len, image, ids = batch["wav"], batch["wav_len"], batch["image"], batch["id"]
         self.clip.update_device(self.device)
         branches = None
-        if _OVERLAP_IMAGE_TOWER and image.is_cuda:
+        # A trainable image tower (clip.image_encoder_trainable) runs on the CURRENT stream, in train and in eval mode: the side-stream overlap below is for
+        # the frozen tower only -- its autograd node, its saved activations and the vision operands that CLIP.packed() rebuilds after every optimizer
+        # step all belong to the stream the backward and the optimizer run on.
+        if _OVERLAP_IMAGE_TOWER and image.is_cuda and not self.clip.image_encoder_trainable:
             # The frozen image tower does not depend on the speech tower: it runs on a side HIP stream and fills the CUs the speech tower's
             # kernels leave idle (GEMM tails, HBM-bound conv0 / LayerNorm phases): 45.9 -> 44.7 ms per B = 256 step.  SC_OVERLAP_VIT=0: serial.
             cur = torch.cuda.current_stream()
@@ -639,7 +642,11 @@ class KWClip_GeneralTransformer(KWClipBase):
             branches = self._branches(audio_feat, audio_len)
             ops.PROFILE_TAG = "speech"
         c_feat, p_feat, vq, kw = branches
-        image_feat = ops.l2norm(image_feat)
+        if image_feat.requires_grad:
+            from ..train_tail import L2NormFn
+            image_feat = L2NormFn.apply(image_feat)
+        else:
+            image_feat = ops.l2norm(image_feat)
         loss_feats = {"id": ids, "image_feat": image_feat}
         log_metrics = {}
         if c_feat is not None:

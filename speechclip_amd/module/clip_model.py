@@ -145,11 +145,14 @@ class CLIP(nn.Module):
         nn.init.normal_(self.positional_embedding, std=0.01)
         nn.init.normal_(self.text_projection, std=cfg.text_width ** -0.5)
         self._packed = None
+        self._packed_vis_key = -1
+        self._vis_params = None
         self._packed_bwd = None
         self.register_load_state_dict_post_hook(lambda module, keys: module.invalidate_packed())
 
     def invalidate_packed(self):
         self._packed = None
+        self._vis_params = None
         self._packed_bwd = None
 
     def packed_bwd(self, dev):
@@ -170,6 +173,7 @@ class CLIP(nn.Module):
 
     def _apply(self, fn, *a, **k):
         self._packed = None
+        self._vis_params = None
         self._packed_bwd = None
         return super()._apply(fn, *a, **k)
 
@@ -177,25 +181,45 @@ class CLIP(nn.Module):
     def dtype(self):
         return self.visual.conv1.weight.dtype
 
-    def _pack(self, dev):
+    def _pack_vis(self, dev):
         bf, f32 = torch.bfloat16, torch.float32
         v, cfg = self.visual, self.cfg
         K = 3 * v.patch * v.patch
         Kpad = (K + 63) // 64 * 64
         w = torch.zeros(cfg.vision_width, Kpad, device=dev, dtype=bf)
         w[:, :K] = v.conv1.weight.detach().reshape(cfg.vision_width, K).to(dev, bf)
-        P = dict(Kpad=Kpad, conv_w=w, cls=v.class_embedding.detach().to(dev, f32), pos=v.positional_embedding.detach().to(dev, f32).contiguous(),
-                 ln_pre=(v.ln_pre.weight.detach().to(dev, f32), v.ln_pre.bias.detach().to(dev, f32)),
-                 ln_post=(v.ln_post.weight.detach().to(dev, f32), v.ln_post.bias.detach().to(dev, f32)),
-                 proj_t=v.proj.detach().t().to(dev, bf).contiguous(), vis=v.transformer.pack(dev),
-                 txt=self.transformer.pack(dev), txt_pos=self.positional_embedding.detach().to(dev, f32).contiguous(),
+        return dict(Kpad=Kpad, conv_w=w, cls=v.class_embedding.detach().to(dev, f32), pos=v.positional_embedding.detach().to(dev, f32).contiguous(),
+                    ln_pre=(v.ln_pre.weight.detach().to(dev, f32), v.ln_pre.bias.detach().to(dev, f32)),
+                    ln_post=(v.ln_post.weight.detach().to(dev, f32), v.ln_post.bias.detach().to(dev, f32)),
+                    proj_t=v.proj.detach().t().to(dev, bf).contiguous(), vis=v.transformer.pack(dev))
+
+    def _pack(self, dev):
+        bf, f32 = torch.bfloat16, torch.float32
+        P = self._pack_vis(dev)
+        P.update(txt=self.transformer.pack(dev), txt_pos=self.positional_embedding.detach().to(dev, f32).contiguous(),
                  ln_final=(self.ln_final.weight.detach().to(dev, f32), self.ln_final.bias.detach().to(dev, f32)),
                  txt_proj_t=self.text_projection.detach().t().to(dev, bf).contiguous())
         return P
 
+    def _vis_key(self):
+        """What the vision operands were built from, as module/hubert.py keys its packed operands: ops.param_epoch moves on FusedAdam steps (raw-pointer
+        writes), the tensors' own `_version` on any torch optimizer step or in-place edit.  A frozen tower (no trainable tensor) never repacks."""
+        if self._vis_params is None:          # the Parameter objects of `visual` (kept by .to() / load_state_dict); dropped with the pack
+            self._vis_params = list(self.visual.parameters())
+        trainable = [p for p in self._vis_params if p.requires_grad]
+        return (ops.param_epoch(*trainable), sum(p._version for p in trainable)) if trainable else -1
+
     def packed(self, dev):
+        """The eval path's operands.  Built by the caller on ITS current stream; the vision part is rebuilt there whenever an optimizer step has moved
+        trainable `visual` weights (a trainable image tower runs on the current stream only: KWClip_GeneralTransformer.forward)."""
         if self._packed is None:
             self._packed = self._pack(dev)
+            self._packed_vis_key = self._vis_key()
+        else:
+            key = self._vis_key()
+            if key != self._packed_vis_key:
+                self._packed.update(self._pack_vis(dev))
+                self._packed_vis_key = key
         return self._packed
 
     @torch.no_grad()
@@ -213,6 +237,12 @@ class CLIP(nn.Module):
         run_tower(P["vis"], x, B, ntok, v.transformer.heads)
         cls = ops.layernorm(x, *P["ln_post"], rows=B, D=W, ld_in=ntok * W)
         return ops.gemm(cls, P["proj_t"], out_f32=True)
+
+    def encode_image_train(self, image: torch.Tensor) -> torch.Tensor:
+        """encode_image with gradients for every `visual` tensor (train_vit.ImageTowerTrainFn): the same kernels at the same rounding points, so the
+        same bits as encode_image."""
+        from ..train_vit import encode_image_train
+        return encode_image_train(self, image)
 
     def encode_text_embeddings(self, emb: torch.Tensor, take_pos) -> torch.Tensor:
         """emb: f32 [B, L, tw] token embeddings (before positional add), L <= context_length; take_pos: int64 [B] or one int for all rows.  Runs the causal text

@@ -49,8 +49,9 @@ class ClipModel(nn.Module):
                  reduce_subword_embbedding: str = None, clip_config: ClipConfig = None, **kwargs):
         super().__init__()
         assert name in _clip_models
-        if image_encoder_trainable or text_encoder_trainable:
-            raise NotImplementedError("CLIP towers are frozen in every shipped config; fine-tuning needs backward kernels")
+        if text_encoder_trainable:
+            raise NotImplementedError("text_encoder_trainable: fine-tuning the CLIP text tower is not built on the MI355X path (its backward yields the "
+                                      "gradient of the input embeddings only); the image tower trains with image_encoder_trainable")
         self.name, self.device = name, device
         if clip_config is not None and not isinstance(clip_config, ClipConfig):
             clip_config = ClipConfig(**dict(clip_config.to_dict() if hasattr(clip_config, "to_dict") else clip_config))
@@ -78,6 +79,9 @@ class ClipModel(nn.Module):
         self.tokenizer = _TokenizerIds(cfg.vocab_size)
         for p in self.model.parameters():
             p.requires_grad = False
+        if image_encoder_trainable:          # clip_official.py `freeze_models`: model.visual stays trainable, everything else is frozen
+            for p in self.model.visual.parameters():
+                p.requires_grad = True
         self.selected_text_emb_ids = None
         if reduce_subword_embbedding is not None:
             if not os.path.exists(reduce_subword_embbedding):
@@ -96,7 +100,7 @@ class ClipModel(nn.Module):
             self.endOfTxt_reduced = self.original2Reduced[self.tokenizer.encoder["<|endoftext|>"]]
 
     def trainable_params(self) -> list:
-        return []
+        return list(self.model.visual.parameters()) if self.image_encoder_trainable else []
 
     def update_device(self, device):
         self.device = device
@@ -113,6 +117,8 @@ class ClipModel(nn.Module):
         return normalize_u8(load_images_u8(paths, self.model.cfg.image_resolution), self.device)
 
     def encode_image(self, image: torch.Tensor) -> torch.Tensor:
+        if self.image_encoder_trainable and torch.is_grad_enabled():
+            return self.model.encode_image_train(image)          # differentiable: train_vit.ImageTowerTrainFn
         return self.model.encode_image(image)
 
     def _special_ids(self):

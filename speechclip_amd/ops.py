@@ -854,8 +854,9 @@ def mix_softmax_bwd(w, dalpha_b, dw):
     return dw
 
 
-def infonce_fwd_bwd(feat_a, feat_b, ids=None, inv_temperature=1.0 / 0.07, margin=0.0, dcl=False, a2b=True, b2a=True):
-    """Loss and its gradients in one go: returns (out3, dfeat_a [Bg,E], dinv scalar tensor) -- d loss/d feat_a and d loss/d inv_temperature."""
+def infonce_fwd_bwd(feat_a, feat_b, ids=None, inv_temperature=1.0 / 0.07, margin=0.0, dcl=False, a2b=True, b2a=True, want_dfeat_b=False):
+    """Loss and its gradients in one go: returns (out3, dfeat_a [Bg,E], dinv scalar tensor) -- d loss/d feat_a and d loss/d inv_temperature;
+    with want_dfeat_b a fourth value, dfeat_b [Bg,E] = inv_temperature * G^T feat_a from the same G = d loss / d logits."""
     _f32c(feat_a, feat_b)
     Bg, E = feat_a.shape
     dev = feat_a.device
@@ -871,6 +872,8 @@ def infonce_fwd_bwd(feat_a, feat_b, ids=None, inv_temperature=1.0 / 0.07, margin
     check(lib().sc_infonce_bwd(ptr(feat_a), ptr(feat_b), ptr(ids), ptr(ws), ptr(ws2), ptr(G), ptr(dinv), Bg, E, inv_temperature, margin, int(dcl),
                                int(a2b), int(b2a), stream()), "sc_infonce_bwd")
     da = sgemm(G, feat_b, alpha=inv_temperature)
+    if want_dfeat_b:
+        return out, da, dinv, sgemm(G, feat_a, transa=True, alpha=inv_temperature)
     return out, da, dinv
 
 
@@ -1152,6 +1155,37 @@ def gelu_bwd_bf16(u, dh):
     du = torch.empty_like(u)
     check(lib().sc_gelu_bwd_bf16(ptr(u), ptr(dh), ptr(du), u.numel(), stream()), "sc_gelu_bwd_bf16")
     return du
+
+
+def quickgelu_bwd_bf16(u, dh, out=None):
+    """du bf16 = dh * quickgelu'(u) (train_vit.hip): u, dh bf16 of one shape, contiguous (any length, views at any element offset)."""
+    _need_cuda(u, dh, out)
+    assert u.dtype == bf16 and dh.dtype == bf16 and u.is_contiguous() and dh.is_contiguous() and u.shape == dh.shape
+    du = torch.empty_like(u) if out is None else out
+    assert du.dtype == bf16 and du.is_contiguous() and du.shape == u.shape
+    check(lib().sc_quickgelu_bwd_bf16(ptr(u), ptr(dh), ptr(du), u.numel(), stream()), "sc_quickgelu_bwd_bf16")
+    return du
+
+
+def vit_embed_bwd(dx, patch, cls, pos, gamma, B, ntok, D, eps=1e-5, out=None):
+    """Adjoint of vit_embed: dx f32 [B*ntok, D], the forward's patch bf16 [B*(ntok-1), D], cls f32 [D], pos f32 [ntok, D], gamma f32 [D]
+    -> (dpatch bf16 [B*(ntok-1), D], dpos f32 [ntok, D], dcls = dpos[0] (a view), dgamma f32 [D], dbeta f32 [D]); out = (dpatch, dpos, dgamma, dbeta) to fill."""
+    _need_cuda(patch)
+    _f32c(dx, cls, pos, gamma)
+    assert patch.dtype == bf16 and patch.is_contiguous() and tuple(patch.shape) == (B * (ntok - 1), D), (tuple(patch.shape), B, ntok, D)
+    assert tuple(dx.shape) == (B * ntok, D) and cls.numel() == D and tuple(pos.shape) == (ntok, D) and gamma.numel() == D
+    dev = patch.device
+    if out is None:
+        out = (torch.empty_like(patch), torch.empty(ntok, D, device=dev, dtype=torch.float32), torch.empty(D, device=dev, dtype=torch.float32),
+               torch.empty(D, device=dev, dtype=torch.float32))
+    dpatch, dpos, dgamma, dbeta = out
+    assert dpatch.dtype == bf16 and dpatch.is_contiguous() and dpatch.shape == patch.shape
+    _f32c(dpos, dgamma, dbeta)
+    assert tuple(dpos.shape) == (ntok, D) and dgamma.numel() == D and dbeta.numel() == D
+    ws = torch.empty(max(1, int(lib().sc_vit_embed_bwd_workspace_bytes(B, ntok, D))), device=dev, dtype=torch.uint8)
+    check(lib().sc_vit_embed_bwd(ptr(dx), ptr(patch), ptr(cls), ptr(pos), ptr(gamma), ptr(dpatch), ptr(dpos), ptr(dgamma), ptr(dbeta), ptr(ws), B, ntok, D,
+                                 eps, stream()), "sc_vit_embed_bwd")
+    return dpatch, dpos, dpos[0], dgamma, dbeta
 
 
 def layernorm_bwd_bf16(x, dy, gamma, eps=1e-5, want_param_grads=True):

@@ -23,7 +23,7 @@ from typing import List, Sequence
 import torch
 
 from . import ops
-from .ops import ACT_GELU
+from .ops import ACT_GELU, ACT_QUICKGELU
 
 BF = torch.bfloat16
 PER_LAYER = 16     # q_w q_b k_w k_b v_w v_b o_w o_b ln1_w ln1_b fc1_w fc1_b fc2_w fc2_b ln2_w ln2_b
@@ -137,6 +137,10 @@ def _attn_bwd(pk, qkv, att, datt, B, Tp, H, valid_i32, drop=None):
 
 
 ATTN_HUBERT = (_attn_fwd, _attn_bwd)     # the layer bodies' default attention pair (head_dim 64); train_branch.py passes the head_dim 64 / 96 / 128 pair
+# The MLP activation of the pre-LN bodies as (GEMM epilogue flag, backward du = f(u, dh)): erf-GELU (fairseq, nn.TransformerEncoderLayer) unless the caller
+# passes another pair -- train_vit.py passes ACT_QUICKGELU_PAIR (CLIP's QuickGELU).
+ACT_GELU_PAIR = (ACT_GELU, ops.gelu_bwd_bf16)
+ACT_QUICKGELU_PAIR = (ACT_QUICKGELU, ops.quickgelu_bwd_bf16)
 
 
 def _site_seeds(seed, count):
@@ -180,10 +184,11 @@ def _layer_fwd_post_ln(h, wqkv, bqkv, p, pk, shape, valid_i32, out, drop, seeds,
     return [h, qkv, att, y1, x1, hm, y2]
 
 
-def _layer_fwd_pre_ln(h, wqkv, bqkv, p, pk, shape, valid_i32, out, drop, seeds, attn=None):
+def _layer_fwd_pre_ln(h, wqkv, bqkv, p, pk, shape, valid_i32, out, drop, seeds, attn=None, act=None):
     """Pre-LN layers ([3P fairseq] layer_norm_first, HuBERT-large): x += attn(LN1 x); x += fc2(gelu(fc1(LN2 x))) on an fp32 residual stream.
     h / out are f32; the saved copies of the stream (LayerNorm inputs of the backward) are bf16.  The large checkpoint's dropouts are 0, so
-    HuBERT passes drop = None; with `drop` (the parallel branch, train_branch.py) each bf16 branch output is dropped before its fp32 residual add."""
+    HuBERT passes drop = None; with `drop` (the parallel branch, train_branch.py) each bf16 branch output is dropped before its fp32 residual add.
+    act: the MLP activation pair, None = ACT_GELU_PAIR."""
     B, Tp, H, eps = shape
     M, d = h.shape
     ow, ob, g1, b1n, w1, b1, w2, b2, g2, b2n = p
@@ -191,11 +196,12 @@ def _layer_fwd_pre_ln(h, wqkv, bqkv, p, pk, shape, valid_i32, out, drop, seeds, 
     qkv = _qkv_rows(pk, M, Tp, d, h.device)
     ops.gemm(t1, wqkv, bqkv, out=qkv[:M])
     attn_fwd = (attn or ATTN_HUBERT)[0]
+    act_flag = (act or ACT_GELU_PAIR)[0]
     if drop is None:
         att = attn_fwd(pk, qkv, M, B, Tp, H, valid_i32)
         xmid = ops.gemm(att, _w16(ow), _f32(ob), residual=h, out_f32=True)
         t2 = ops.layernorm(xmid, _f32(g2), _f32(b2n), eps)
-        hm = ops.gemm(t2, _w16(w1), _f32(b1), ACT_GELU)
+        hm = ops.gemm(t2, _w16(w1), _f32(b1), act_flag)
         ops.gemm(hm, _w16(w2), _f32(b2), residual=xmid, out=out, out_f32=True)
     else:       # x += dropout1(attn(LN1 x));  x += dropout3(fc2(dropout2(gelu(fc1(LN2 x)))))
         sa, s1, s2, s3 = seeds
@@ -204,7 +210,7 @@ def _layer_fwd_pre_ln(h, wqkv, bqkv, p, pk, shape, valid_i32, out, drop, seeds, 
         ops.dropout_bf16(o, drop["hidden"], s1, out=o)
         xmid = h + o.float()
         t2 = ops.layernorm(xmid, _f32(g2), _f32(b2n), eps)
-        hm = ops.gemm(t2, _w16(w1), _f32(b1), ACT_GELU)
+        hm = ops.gemm(t2, _w16(w1), _f32(b1), act_flag)
         if drop["activation"] > 0:
             ops.dropout_bf16(hm, drop["activation"], s2, out=hm)
         f = ops.gemm(hm, _w16(w2), _f32(b2))
@@ -244,7 +250,7 @@ def _layer_bwd_post_ln(g, acts, p, pk, shape, valid_i32, want, drop, seeds, attn
     return dh, (dqkv, h, dy1, att, du, x1, dy2, hm, dg1, db1n, dg2, db2n) if want else None
 
 
-def _layer_bwd_pre_ln(g, acts, p, pk, shape, valid_i32, want, drop, seeds, attn=None):
+def _layer_bwd_pre_ln(g, acts, p, pk, shape, valid_i32, want, drop, seeds, attn=None, act=None):
     B, Tp, H, eps = shape
     h16, qkv, att, xmid16, t1, hm, t2 = acts
     qw, qb, kw, kb, vw, vb, ow, ob, g1, b1n, w1, b1, w2, b2, g2, b2n = p
@@ -255,7 +261,7 @@ def _layer_bwd_pre_ln(g, acts, p, pk, shape, valid_i32, want, drop, seeds, attn=
     if drop is not None and drop["activation"] > 0:
         ops.dropout_bf16(dhm, drop["activation"], s2, out=dhm)
     u = ops.gemm(t2, _w16(w1), _f32(b1))
-    du = ops.gelu_bwd_bf16(u, dhm)
+    du = (act or ACT_GELU_PAIR)[1](u, dhm)
     del u, dhm
     dt2 = ops.gemm(du, _w16(w1.t()))
     dxm, dg2, db2n = ops.layernorm_bwd_bf16(xmid16, dt2, _f32(g2), eps, want)

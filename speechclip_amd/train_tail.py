@@ -485,29 +485,30 @@ class L2NormFn(torch.autograd.Function):
 
 
 class MaskedContrastiveFn(torch.autograd.Function):
-    """loss = MaskedContrastiveLoss(feat_a, feat_b, ids); gradients for feat_a and (if given) the log-temperature parameter."""
+    """loss = MaskedContrastiveLoss(feat_a, feat_b, ids); gradients for feat_a, for feat_b when it carries one (a trainable image tower:
+    dfeat_b = inv_t G^T feat_a from the same G = d loss / d logits) and (if given) the log-temperature parameter."""
 
     @staticmethod
     def forward(ctx, feat_a, feat_b, ids, log_temp, inv_t, margin, dcl, a2b, b2a):
         if log_temp is not None:
             inv_t = float(log_temp.detach().float().exp().item())
-        out, da, dinv = ops.infonce_fwd_bwd(feat_a.detach().float().contiguous(), feat_b.detach().float().contiguous(), ids, inv_t, margin, dcl, a2b, b2a)
-        ctx.save_for_backward(da, dinv)
+        want_b = bool(feat_b.requires_grad)
+        out, da, dinv, *db = ops.infonce_fwd_bwd(feat_a.detach().float().contiguous(), feat_b.detach().float().contiguous(), ids, inv_t, margin, dcl, a2b, b2a,
+                                                 want_dfeat_b=want_b)
+        ctx.save_for_backward(da, dinv, *db)
         ctx.inv_t, ctx.has_temp = inv_t, log_temp is not None
-        if feat_b.requires_grad:
-            raise NotImplementedError("image-side gradients: the CLIP tower and its projection are frozen in every shipped config")
         return out[0].clone()
 
     @staticmethod
     def backward(ctx, dloss):
-        da, dinv = ctx.saved_tensors
+        da, dinv, *db = ctx.saved_tensors
         g = dloss.float()
         # inv_t = exp(param).  Every rank evaluates the FULL global loss, so every rank holds the full d loss / d log-temperature, while
         # FusedAdam SUMS the flat gradient over ranks (right for the branch weights, whose per-rank gradients are partial sums through the
         # local rows): the temperature's share is therefore 1/ws per rank.
         ws = parallel.world()[1]
         dtemp = (dinv * (ctx.inv_t / ws) * g).reshape(()) if ctx.has_temp else None
-        return da * g, None, None, dtemp, None, None, None, None, None
+        return da * g, (db[0] * g if db else None), None, dtemp, None, None, None, None, None
 
 
 class PackedGatherFn(torch.autograd.Function):
