@@ -69,6 +69,42 @@ def worst(err, bound):
     return (float(ratio.reshape(-1)[i]) if ratio.numel() else 0.0), i
 
 
+# ================================================================================================ what every GPU parity test shares
+GUARD = 64
+
+
+class Guarded:
+    """a [rows, ld] window inside a sentinel-filled flat buffer; columns < width of every row are the region a kernel may write"""
+
+    def __init__(self, rows, ld, dt, width=None):
+        self.rows, self.ld, self.width = rows, ld, ld if width is None else width
+        self.sent = SENT32 if dt == F32 else SENT16
+        self.buf = torch.full((2 * GUARD + rows * ld,), self.sent, dtype=dt, device="cuda")
+        self.win = self.buf[GUARD:GUARD + rows * ld].view(rows, ld)
+
+    def out(self):
+        return self.win[:, :self.width]
+
+    def check(self, what):
+        flat = self.buf.cpu().to(F64)
+        written = torch.zeros(flat.numel(), dtype=torch.bool)
+        w = written[GUARD:GUARD + self.rows * self.ld].view(self.rows, self.ld)
+        w[:, :self.width] = True
+        assert bool((flat[~written] == self.sent).all()), (what, "wrote outside its output region")
+        return flat[GUARD:GUARD + self.rows * self.ld].view(self.rows, self.ld)[:, :self.width].clone()
+
+
+def judge(what, got, ref, bound, shape=None):
+    got = got.reshape(ref.shape)
+    err = (got - ref).abs()
+    r, i = worst(err, bound)
+    idx = tuple(int(v) for v in torch.unravel_index(torch.tensor(i), ref.shape)) if ref.numel() else ()
+    print(f"{what:60s} worst err/bound {r:8.4f} at {idx}")
+    assert torch.isfinite(got).all(), what
+    assert r <= 1.0, (what, "err / bound", r, "at", idx, "got", float(got[idx]), "ref", float(ref[idx]), "bound", float(bound[idx]))
+    return r
+
+
 # ================================================================================================ LayerNorm
 LNCase = collections.namedtuple("LNCase", "id path D in_dt out_dt affine gelu ld_in ld_out x_off rows")
 LN_ROWS = (1, 2, 3, 7, 8, 9, 15, 16, 17, 33)

@@ -27,7 +27,7 @@ import row_kernels_ref as R
 
 pytestmark = pytest.mark.gpu
 F64, F32, BF, H16 = R.F64, R.F32, R.BF, R.H16
-GUARD = 64
+GUARD = R.GUARD
 
 
 def _dev(t, dt):
@@ -38,36 +38,7 @@ def _i32(v):
     return torch.tensor(list(v), dtype=torch.int32, device="cuda")
 
 
-class Guarded:
-    """a [rows, ld] window inside a sentinel-filled flat buffer; columns < width of every row are the region a kernel may write"""
-
-    def __init__(self, rows, ld, dt, width=None):
-        self.rows, self.ld, self.width = rows, ld, ld if width is None else width
-        self.sent = R.SENT32 if dt == F32 else R.SENT16
-        self.buf = torch.full((2 * GUARD + rows * ld,), self.sent, dtype=dt, device="cuda")
-        self.win = self.buf[GUARD:GUARD + rows * ld].view(rows, ld)
-
-    def out(self):
-        return self.win[:, :self.width]
-
-    def check(self, what):
-        flat = self.buf.cpu().to(F64)
-        written = torch.zeros(flat.numel(), dtype=torch.bool)
-        w = written[GUARD:GUARD + self.rows * self.ld].view(self.rows, self.ld)
-        w[:, :self.width] = True
-        assert bool((flat[~written] == self.sent).all()), (what, "wrote outside its output region")
-        return flat[GUARD:GUARD + self.rows * self.ld].view(self.rows, self.ld)[:, :self.width].clone()
-
-
-def _judge(what, got, ref, bound, shape=None):
-    got = got.reshape(ref.shape)
-    err = (got - ref).abs()
-    r, i = R.worst(err, bound)
-    idx = tuple(int(v) for v in torch.unravel_index(torch.tensor(i), ref.shape)) if ref.numel() else ()
-    print(f"{what:60s} worst err/bound {r:8.4f} at {idx}")
-    assert torch.isfinite(got).all(), what
-    assert r <= 1.0, (what, "err / bound", r, "at", idx, "got", float(got[idx]), "ref", float(ref[idx]), "bound", float(bound[idx]))
-    return r
+Guarded, _judge = R.Guarded, R.judge
 
 
 def _strided_input(x64, dt, ld, off=0, col0=0):
