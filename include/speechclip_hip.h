@@ -508,6 +508,30 @@ int sc_unpack_rows(const void* src, int64_t src_layer_stride_bytes, const int32_
 int sc_pack_rows(const void* src, int64_t src_layer_stride_bytes, const int32_t* row_off, void* out, int64_t out_layer_stride_bytes, int n_layers,
                  int B, int T_in, int64_t total_rows, int row_bytes, int halo, void* stream);
 
+/* ---- CLIP text tower on packed rows (speech-text retrieval: ClipModel.encode_text with SC_TEXT_PACK=1, clip_official.py:211-218).  Caption b owns rows
+ * [row_off[b], row_off[b + 1]) = its positions SOT .. EOT (row_off: B + 1 device int32, row_off[0] = 0, row_off[B] = total_rows): under the causal mask nothing
+ * behind a caption's EOT reaches its feature, so those positions are not computed.  GEMMs and LayerNorms take the rows as they are.
+ *   sc_text_embed_packed   out[row_off[b] + t][:] = tok[ids[b * ld_ids + t]][:] + pos[t][:] for t < row_off[b + 1] - row_off[b]; ids int64 [B, L] (row stride
+ *                          ld_ids >= L), tok fp32 [V, W], pos fp32 [ctx, W], out fp32 [total_rows, W].  One fp32 add per element, float4 loads and stores,
+ *                          nothing else is written.  PRECONDITION: every id in [0, V) and rows per caption <= min(L, ctx) (the caller checks both where it
+ *                          finds the EOT positions); the kernel itself stays inside its operands (rows beyond L are not written, an id outside the table reads
+ *                          the table's first / last row).  W % 4 != 0, a null operand, L > ctx, ld_ids < L or a misaligned table return an error, no launch.
+ *   sc_attention_fwd_text  causal attention over packed rows, head_dim 64, bf16, operands as sc_attention_fwd_packed (head h at column h*64, ld_qkv / ld_out
+ *                          multiples of 8, rows per caption <= Tmax): query t of caption b sees keys 0 .. t of caption b only.  No dropout, no SC_ATTN_F16, no klens.
+ *                          Two forms.  GENERAL (any Tmax; forced by SC_ATTN_TEXT_GENERAL): sc_attention_fwd's kernel with row_off and the causal bit -- with
+ *                          row_off[b] = b*T it returns sc_attention_fwd(..., SC_ATTN_CAUSAL) bit for bit.  SHORT-ROW (the default when Tmax <= 128; measured,
+ *                          profiles/text_tower_bench.txt): one wave per (caption, head) unit, S = K.Q^T and P.V on v_mfma_f32_16x16x32_bf16 over the caption's
+ *                          whole key range at once, fp32 scores and softmax in registers (no online rescale), every output row written once, no atomics; the
+ *                          same roundings as the general form (P to bf16 before P.V, the row sum over the unrounded P, one rounding of the output).
+ *                          Both forms: no row outside [row_off[b], row_off[b + 1]) is read for caption b (rows before the first and behind the last caption
+ *                          may hold anything); V rows INSIDE a caption must be finite, as for sc_attention_fwd (keys behind the diagonal enter the P.V MFMA
+ *                          with P = 0).  Any flag bit other than SC_ATTN_TEXT_GENERAL is refused. */
+#define SC_ATTN_TEXT_GENERAL 0x100
+int sc_text_embed_packed(const int64_t* ids, int64_t ld_ids, const float* tok, const float* pos, const int32_t* row_off, float* out,
+                         int B, int L, int V, int ctx, int W, int64_t total_rows, void* stream);
+int sc_attention_fwd_text(const void* q, const void* k, const void* v, void* out, const int32_t* row_off, int B, int H, int Tmax,
+                          int64_t total_rows, int head_dim, int64_t ld_qkv, int64_t ld_out, float scale, int flags, void* stream);
+
 /* ---- Fused attention backward over packed rows (fine-tuning on the padding-free layout), head_dim 64.  Operands as sc_attention_fwd_packed: bf16 rows,
  * head h at column h*64, utterance b at rows row_off[b] .. (row_off[B] == total_rows; rows per utterance <= Tmax), klens[b] valid keys; row_off == NULL:
  * the uniform layout row_off[b] = b*Tmax (total_rows = B*Tmax).  O / dO: the forward's output and its gradient (row stride ld_o); dq / dk / dv: row stride

@@ -18,6 +18,7 @@ GEMM_OUT_F32 = 0x10
 GEMM_F16 = 0x20          # SC_GEMM_F16: IEEE-half operands (and 16-bit outputs)
 ATTN_CAUSAL, ATTN_F16 = 0x1, 0x2
 ATTN_HD_OUT_F32 = 0x10
+ATTN_TEXT_GENERAL = 0x100          # SC_ATTN_TEXT_GENERAL (sc_attention_fwd_text)
 
 _lib = None
 
@@ -108,6 +109,8 @@ def _declare(L):
         "sc_reverse_rows_packed_bf16": ([P, P, P, I, L64, I, P], c_int),
         "sc_posconv_pack_gapped": ([P, P, P, P, I, L64, I, I, I, I, L64, P], c_int),
         "sc_attention_fwd_packed": ([P, P, P, P, P, P, I, I, I, L64, I, L64, L64, F, F, U32, I, P], c_int),
+        "sc_text_embed_packed": ([P, L64, P, P, P, P, I, I, I, I, I, L64, P], c_int),
+        "sc_attention_fwd_text": ([P, P, P, P, P, I, I, I, L64, I, L64, L64, F, I, P], c_int),
         "sc_unpack_rows": ([P, L64, P, P, L64, I, I, I, I, I, P], c_int),
         "sc_pack_rows": ([P, L64, P, P, L64, I, I, I, L64, I, I, P], c_int),
         "sc_attention_bwd_packed_workspace_bytes": ([L64, I], c_int64),

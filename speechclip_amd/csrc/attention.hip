@@ -769,6 +769,31 @@ extern "C" int sc_attention_fwd_packed(const void* q, const void* k, const void*
     return attention_fwd_impl(q, k, v, out, klens, B, H, Tmax, head_dim, ld_qkv, ld_out, scale, flags, drop_p, seed, stream, row_off, total_rows);
 }
 
+// CLIP text tower on packed rows: caption b owns rows [row_off[b], row_off[b + 1]), query t sees keys 0 .. t of its own caption.  attn_fwd_kernel with
+// row_off AND the causal bit: T and the row base come from row_off, the key-tile count is cut at the block's last query, key rows are clamped to the
+// caption's last row on load (no row of a neighbour is read) and the mask compares caption-local indices.  That is the GENERAL form (any Tmax,
+// SC_ATTN_TEXT_GENERAL forces it).  Up to SC_TEXT_ATTN_SHORT_MAX rows per caption the default is the short-row form (text_tower.hip: one wave per
+// (caption, head) unit) -- measured, profiles/text_tower_bench.txt.
+constexpr int SC_TEXT_ATTN_SHORT_MAX = 128;
+int text_attn_short_launch(const void* q, const void* k, const void* v, void* out, const int32_t* row_off, int B, int H, int Tmax, int64_t total_rows,
+                           int64_t ld_qkv, int64_t ld_out, float scale, void* stream);
+
+extern "C" int sc_attention_fwd_text(const void* q, const void* k, const void* v, void* out, const int32_t* row_off, int B, int H, int Tmax,
+                                     int64_t total_rows, int head_dim, int64_t ld_qkv, int64_t ld_out, float scale, int flags, void* stream) {
+    SC_CHECK_ARG((flags & ~SC_ATTN_TEXT_GENERAL) == 0, "sc_attention_fwd_text: unknown flag bits 0x%x (SC_ATTN_TEXT_GENERAL only: bf16, no dropout)", flags);
+    SC_CHECK_ARG(head_dim == 64, "sc_attention_fwd_text: head_dim=%d unsupported (64 only)", head_dim);
+    SC_CHECK_ARG(row_off != nullptr, "sc_attention_fwd_text: row_off is required");
+    SC_CHECK_ARG(q != nullptr && k != nullptr && v != nullptr && out != nullptr, "sc_attention_fwd_text: q, k, v and out are required");
+    SC_CHECK_ARG(Tmax > 0 || B <= 0, "sc_attention_fwd_text: Tmax=%d", Tmax);
+    SC_CHECK_ARG(ld_qkv % 8 == 0 && ld_out % 8 == 0, "sc_attention_fwd_text: ld_qkv and ld_out must be multiples of 8 (16-byte rows)");
+    SC_CHECK_ARG((((uintptr_t)q | (uintptr_t)k | (uintptr_t)v | (uintptr_t)out) & 15) == 0, "sc_attention_fwd_text: misaligned pointers");
+    SC_CHECK_ARG(H > 0, "sc_attention_fwd_text: H=%d", H);
+    if (B <= 0 || total_rows <= 0) return 0;
+    if (!(flags & SC_ATTN_TEXT_GENERAL) && Tmax <= SC_TEXT_ATTN_SHORT_MAX)
+        return text_attn_short_launch(q, k, v, out, row_off, B, H, Tmax, total_rows, ld_qkv, ld_out, scale, stream);
+    return attention_fwd_impl(q, k, v, out, nullptr, B, H, Tmax, head_dim, ld_qkv, ld_out, scale, SC_ATTN_CAUSAL, 0.f, 0u, stream, row_off, total_rows);
+}
+
 extern "C" int sc_cls_attention_fwd(const void* cls_qkv, const void* kv_x, int64_t ld_kv, const int32_t* lens, void* out, int B, int T,
                                     int NQ, int H, int head_dim, float scale, void* stream) {
     SC_CHECK_ARG(NQ >= 1 && NQ <= 8, "sc_cls_attention_fwd: NQ=%d must be in [1,8]", NQ);

@@ -79,6 +79,27 @@ class KWClipBase(BaseLightningModel):
             raise TypeError(f"Unknown image type {type(images)}")
         return self.clip.encode_image(images)
 
+    def forward_text(self, sents: Union[list, torch.Tensor]) -> torch.Tensor:
+        """kwClip.py:529-547: sentences (a list, tokenised by ClipModel.prep_text) or a 2-D tensor of token ids -> CLIP text features [B, embed_dim].
+        With a reduced sub-word vocabulary the ids are mapped to reduced ids exactly ONCE: a list by prep_text, a tensor of ORIGINAL ids here, by one
+        lookup-table gather.  (The reference maps a list twice -- in prep_text and again in its double loop here -- which cannot be intended, and
+        overwrites the caller's tensor; neither is restated.)"""
+        text = self.text_ids(sents)
+        return self.clip.encode_text(text.to(self.clip.model.token_embedding.weight.device))
+
+    def text_ids(self, sents: Union[list, torch.Tensor]) -> torch.Tensor:
+        """The id tensor forward_text encodes ([B, L], reduced ids under a reduced vocabulary); the caller's tensor is never written."""
+        if isinstance(sents, list):
+            self.clip.update_device(self.device)
+            text = self.clip.prep_text(sents)
+        elif isinstance(sents, torch.Tensor):
+            if sents.dim() != 2:
+                raise ValueError(f"Incorrect text tensor shape {sents.shape}")
+            text = self.clip.map_to_reduced(sents) if hasattr(self.clip, "original2Reduced") else sents
+        else:
+            raise TypeError(f"Unknown text type {type(sents)}")
+        return text
+
     def forward(self, batch: dict) -> tuple:
         raise NotImplementedError()
 

@@ -91,8 +91,10 @@ class _Tower(nn.Module):
         return out
 
 
-def run_tower(packed, x, B, L, heads, causal=False):
-    """x: f32 residual stream [B*L, W], updated in place.  Pre-LN blocks with QuickGELU MLP."""
+def run_tower(packed, x, B, L, heads, causal=False, row_off=None, text_general=False):
+    """x: f32 residual stream [B*L, W], updated in place.  Pre-LN blocks with QuickGELU MLP.
+    row_off (device int32 [B + 1]): the text tower on packed rows -- sequence b owns rows row_off[b] .. of x (at most L each) and attention is the
+    causal packed form (ops.attention_text; text_general: its SC_ATTN_TEXT_GENERAL bit).  None: uniform rows, the kernels and bits of every caller so far."""
     M, W = x.shape
     dev = x.device
     bf = torch.bfloat16
@@ -103,7 +105,11 @@ def run_tower(packed, x, B, L, heads, causal=False):
     for L_ in packed:
         ops.layernorm(x, *L_["ln1"], out=n)
         ops.gemm(n, L_["wqkv"], L_["bqkv"], out=qkv)
-        ops.attention(qkv, B, L, heads, None, out=att, causal=causal)
+        if row_off is None:
+            ops.attention(qkv, B, L, heads, None, out=att, causal=causal)
+        else:
+            assert causal, "packed rows are served for the causal text tower only"
+            ops.attention_text(qkv, B, L, heads, row_off, out=att, general=text_general)
         ops.gemm(att, L_["wo"], L_["bo"], residual=x, out=x, out_f32=True)
         ops.layernorm(x, *L_["ln2"], out=n)
         ops.gemm(n, L_["w1"], L_["b1"], ACT_QUICKGELU, out=ffn)
@@ -259,6 +265,47 @@ class CLIP(nn.Module):
             return TextTowerTrainFn.apply(self, emb, take_pos)
         with torch.no_grad():
             return self._encode_text_embeddings_eval(emb, take_pos)
+
+    def text_pack_plan(self, text: torch.Tensor) -> dict:
+        """Packed geometry of a caption batch.  text: [B, L] integer ids, L <= context_length.  EOT position = text.argmax(-1) (clip_official.py:211-218);
+        caption b keeps its positions 0 .. EOT.  Checks the id range here, where the ids are looked at anyway: on the host for a CPU tensor, with ONE
+        device-to-host copy (EOT positions, min, max) for a device tensor."""
+        if text.dim() != 2 or text.dtype not in (torch.int64, torch.int32, torch.int16, torch.uint8, torch.int8):
+            raise ValueError(f"text must be a [B, L] integer tensor, got {tuple(text.shape)} {text.dtype}")
+        B, L = text.shape
+        if L > self.context_length or L < 1 or B < 1:
+            raise ValueError(f"text is [{B}, {L}]: need B >= 1 and 1 <= L <= context_length = {self.context_length}")
+        stats = torch.cat([text.argmax(dim=-1), text.min().reshape(1).long(), text.max().reshape(1).long()]).tolist()
+        eot, lo, hi = stats[:B], stats[B], stats[B + 1]
+        V = self.token_embedding.weight.shape[0]
+        if lo < 0 or hi >= V:
+            raise IndexError(f"token ids span [{lo}, {hi}]: outside the embedding table [0, {V})")
+        row_off = [0]
+        for e in eot:
+            row_off.append(row_off[-1] + int(e) + 1)
+        return dict(row_off=row_off, rows_max=max(eot) + 1, total=row_off[-1], B=B, L=L)
+
+    @torch.no_grad()
+    def encode_text_ids(self, text: torch.Tensor, plan: dict = None, general: bool = False) -> torch.Tensor:
+        """[B, L] token ids -> [B, embed_dim] f32, as encode_text (clip_official.py:211-218), on PACKED rows: only positions 0 .. EOT of every caption run
+        through the tower (sc_text_embed_packed, the pre-LN blocks over sum_b (EOT_b + 1) rows with sc_attention_fwd_text, a gather of the B EOT rows,
+        ln_final, text_projection).  Eval only: the text tower is frozen.  head_dim 64 (every ViT-B / ViT-L text tower)."""
+        tw, heads = self.cfg.text_width, self.transformer.heads
+        if tw != heads * 64:
+            raise NotImplementedError(f"packed text tower: head_dim {tw}/{heads} is not 64")
+        tok = self.token_embedding.weight.detach()
+        assert tok.is_cuda, "CLIP.encode_text_ids runs on the HIP kernels only (no CPU fallback)"
+        dev = tok.device
+        plan = self.text_pack_plan(text) if plan is None else plan
+        P = self.packed(dev)
+        B, total = plan["B"], plan["total"]
+        off = torch.tensor(plan["row_off"], dtype=torch.int32).to(dev)
+        ids = text.to(device=dev, dtype=torch.int64)
+        x = ops.text_embed_packed(ids, tok.float().contiguous(), P["txt_pos"], off, total)
+        run_tower(P["txt"], x, B, plan["rows_max"], heads, causal=True, row_off=off, text_general=general)
+        rows = ops.gather_rows(x, off[1:].to(torch.int64) - 1)          # the EOT row is the last row of its caption
+        n = ops.layernorm(rows, *P["ln_final"])
+        return ops.gemm(n, P["txt_proj_t"], out_f32=True)
 
     def _encode_text_embeddings_eval(self, emb: torch.Tensor, take_pos: torch.Tensor) -> torch.Tensor:
         P = self.packed(emb.device)

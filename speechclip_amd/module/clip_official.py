@@ -17,6 +17,10 @@ from .clip_model import CLIP, ClipConfig
 logger = logging.getLogger(__name__)
 _clip_models = {"RN50", "RN101", "RN50x4", "RN50x16", "RN50x64", "ViT-B/32", "ViT-B/16", "ViT-L/14"}
 SOT_ID, EOT_ID = 49406, 49407
+# What SC_TEXT_PACK=auto does: True = pack when that removes at least 10 % of the rows.  tools/text_tower_bench.py measured the packed text tower faster than
+# the padded one in 3 of 3 interleaved passes (5000 captions of 6 .. 30 rows and one of 77, ViT-B/32: 10.5 ms against 41.5 ms, profiles/text_tower_bench.txt).
+# False would keep `auto` on the padded path; SC_TEXT_PACK=1 / 0 decide regardless.
+_TEXT_PACK_AUTO = True
 
 
 class _IdDecoder(dict):
@@ -45,6 +49,10 @@ class _TokenizerIds:
 
 
 class ClipModel(nn.Module):
+    """The reference's ClipModel surface: encode_image / encode_text / encode_keywords / prep_image / prep_text / deTokenize / get_scores.
+    NOT built: `encode_subword` -- in the reference (clip_official.py:266-277) it calls `self.encode_subword_prob`, a method that exists nowhere,
+    so it cannot run there either and there is nothing to restate."""
+
     def __init__(self, name: str, device: str = "cpu", image_encoder_trainable: bool = False, text_encoder_trainable: bool = False,
                  reduce_subword_embbedding: str = None, clip_config: ClipConfig = None, **kwargs):
         super().__init__()
@@ -126,8 +134,92 @@ class ClipModel(nn.Module):
             return self.tokenizer.encoder["<|startoftext|>"], self.tokenizer.encoder["<|endoftext|>"]
         return self.startOfTxt_reduced, self.endOfTxt_reduced
 
+    # ---- text surface (clip_official.py:166-198, 279-289) ------------------------------------------------------------------------------
+    def _to_reduced(self, i: int) -> int:
+        try:
+            return self.original2Reduced[int(i)]
+        except KeyError:
+            raise KeyError(f"token id {int(i)} is not in the reduced vocabulary ({len(self.original2Reduced)} ids)") from None
+
+    def prep_text(self, sents: list) -> torch.Tensor:
+        """clip_official.py:166-180 (`clip.tokenize` restated): sentence -> [SOT] + tokenizer.encode(s) + [EOT], zero padded to context_length; int64
+        [B, context_length] on the CPU.  A sentence that does not fit raises RuntimeError.  With a reduced vocabulary every id (the padding id 0 too, as
+        in the reference) is mapped through original2Reduced ONCE; an id outside it raises KeyError.  Works with any tokenizer object that has `encode`
+        and `encoder["<|startoftext|>"]` / `["<|endoftext|>"]`; the built-in one reads id literals ("<320> <1125>")."""
+        if isinstance(sents, str):
+            sents = [sents]
+        sot, eot = self.tokenizer.encoder["<|startoftext|>"], self.tokenizer.encoder["<|endoftext|>"]
+        L = self.model.context_length
+        reduced = self.selected_text_emb_ids is not None
+        out = torch.full((len(sents), L), self._to_reduced(0) if reduced else 0, dtype=torch.long)
+        for i, s in enumerate(sents):
+            toks = [sot] + [int(t) for t in self.tokenizer.encode(s)] + [eot]
+            if len(toks) > L:
+                raise RuntimeError(f"Input {s!r} is too long for context length {L}: {len(toks)} tokens with <|startoftext|> and <|endoftext|>")
+            if reduced:
+                toks = [self._to_reduced(t) for t in toks]
+            out[i, :len(toks)] = torch.tensor(toks, dtype=torch.long)
+        return out
+
+    def map_to_reduced(self, text: torch.Tensor) -> torch.Tensor:
+        """ORIGINAL ids -> reduced ids by one lookup-table gather (what kwClip.py:538-544 does with a Python double loop); a new tensor, same device.
+        An id outside the reduced vocabulary raises KeyError naming it."""
+        lut = getattr(self, "_orig2reduced_lut", None)
+        if lut is None:
+            n = max(int(max(self.original2Reduced)) + 1, int(self.original_text_emb_weight.shape[0]))
+            lut = torch.full((n,), -1, dtype=torch.long)
+            lut[torch.as_tensor(self.selected_text_emb_ids, dtype=torch.long)] = torch.arange(len(self.selected_text_emb_ids))
+            self._orig2reduced_lut = lut
+        t = text.long()
+        inside = (t >= 0) & (t < lut.numel())
+        out = lut.to(t.device)[t.clamp(0, lut.numel() - 1)]
+        bad = ~inside | (out < 0)
+        if bool(bad.any()):
+            raise KeyError(f"token id {int(t[bad][0])} is not in the reduced vocabulary ({len(self.original2Reduced)} ids)")
+        return out
+
+    def deTokenize(self, sents) -> list:
+        """clip_official.py:182-198: id rows -> strings without the start / end markers.  Differences, both deliberate: the caller's list is NOT mapped
+        in place (the reference overwrites it with original ids), and a row is cut at its first <|endoftext|> (the reference decodes the zero padding
+        behind it too, "!" for every pad position of the real vocabulary)."""
+        if isinstance(sents, torch.Tensor):
+            sents = sents.view(*sents.shape[:2]).tolist()
+        sot, eot = self.tokenizer.encoder["<|startoftext|>"], self.tokenizer.encoder["<|endoftext|>"]
+        res = []
+        for sent in sents:
+            ids = [int(t) for t in sent]
+            if self.selected_text_emb_ids is not None:
+                ids = [self.reducedl2Original[t] for t in ids]
+            if eot in ids:
+                ids = ids[:ids.index(eot)]
+            ids = [t for t in ids if t != sot]
+            res.append(self.tokenizer.decode(ids).replace("<|startoftext|>", "").replace("<|endoftext|>", "").strip())
+        return res
+
+    def get_scores(self, image: torch.Tensor, text: torch.Tensor) -> tuple:
+        """clip_official.py:279-289 (CLIP.forward): (logits_per_image [B_image, B_text], logits_per_text = its transpose), fp32,
+        exp(logit_scale) * l2(encode_image(image)) @ l2(encode_text(text)).T on the device (sc_l2norm_fwd, sc_sgemm)."""
+        from .. import ops
+        with torch.no_grad():
+            img = ops.l2norm(self.encode_image(image).detach().float().contiguous())
+            txt = ops.l2norm(self.encode_text(text).detach().float().contiguous())
+            logits_per_image = ops.sgemm(img, txt, transb=True, alpha=float(self.model.logit_scale.detach().exp()))
+        return logits_per_image, logits_per_image.t()
+
     def encode_text(self, text: torch.Tensor) -> torch.Tensor:
-        """text: [B, 77] token ids (reduced ids if the vocabulary is reduced).  EOT = arg-max id position."""
+        """text: [B, L <= 77] token ids (reduced ids if the vocabulary is reduced).  EOT = arg-max id position.
+        SC_TEXT_PACK = 0: every caption runs at the batch's full length L (the padded path); 1: packed rows (CLIP.encode_text_ids: positions behind a
+        caption's EOT are not computed) whenever the text heads have head_dim 64; auto (default): packed when that removes at least 10 % of the rows
+        AND the packed path has been measured faster (_TEXT_PACK_AUTO, profiles/text_tower_bench.txt), else padded."""
+        mode = os.environ.get("SC_TEXT_PACK", "auto")
+        m = self.model
+        if mode != "0" and m.cfg.text_width == 64 * m.transformer.heads and m.token_embedding.weight.is_cuda:
+            if mode == "1":
+                return m.encode_text_ids(text)
+            if _TEXT_PACK_AUTO and mode == "auto":
+                plan = m.text_pack_plan(text)
+                if plan["total"] <= 0.9 * plan["B"] * plan["L"]:
+                    return m.encode_text_ids(text, plan)
         emb = self.model.token_embedding(text)
         return self.model.encode_text_embeddings(emb, text.argmax(dim=-1))
 

@@ -525,6 +525,40 @@ def attention_packed(qkv, B, rows_max, H, klens_i32, row_off_i32, out=None, drop
     return attention(qkv, B, rows_max, H, klens_i32, out=out, row_off_i32=row_off_i32, drop=(drop_p, seed))
 
 
+def text_embed_packed(ids, tok, pos, row_off_i32, total_rows, out=None):
+    """CLIP text tower on packed rows (sc_text_embed_packed): ids int64 [B, L], tok f32 [V, W], pos f32 [ctx, W] -> f32 [total_rows, W] with
+    out[row_off[b] + t] = tok[ids[b, t]] + pos[t] for t < rows_b.  The caller has checked ids in [0, V) and rows_b <= L."""
+    _need_cuda(ids, tok, pos, row_off_i32)
+    assert ids.dtype == torch.int64 and ids.dim() == 2 and ids.stride(1) == 1
+    assert tok.dtype == torch.float32 and pos.dtype == torch.float32 and tok.is_contiguous() and pos.is_contiguous() and tok.shape[1] == pos.shape[1]
+    B, L = ids.shape
+    assert row_off_i32.dtype == torch.int32 and row_off_i32.numel() == B + 1
+    W = tok.shape[1]
+    if out is None:
+        out = torch.empty(int(total_rows), W, device=tok.device, dtype=torch.float32)
+    assert out.dtype == torch.float32 and out.is_contiguous() and out.shape == (int(total_rows), W)
+    check(lib().sc_text_embed_packed(ptr(ids), ids.stride(0), ptr(tok), ptr(pos), ptr(row_off_i32), ptr(out), B, L, tok.shape[0], pos.shape[0], W,
+                                     int(total_rows), stream()), "sc_text_embed_packed")
+    return out
+
+
+def attention_text(qkv, B, rows_max, H, row_off_i32, out=None, general=False):
+    """Causal attention over packed caption rows (sc_attention_fwd_text): qkv bf16 [total_rows, 3*H*64] (q | k | v), caption b at rows row_off[b] ..
+    (at most rows_max each); query t sees keys 0 .. t of its own caption.  general: SC_ATTN_TEXT_GENERAL."""
+    _need_cuda(qkv, row_off_i32)
+    D = H * 64
+    total = qkv.shape[0]
+    assert qkv.dtype == bf16 and qkv.shape == (total, 3 * D) and qkv.is_contiguous()
+    assert row_off_i32.dtype == torch.int32 and row_off_i32.numel() == B + 1
+    if out is None:
+        out = torch.empty(total, D, device=qkv.device, dtype=bf16)
+    assert out.dtype == bf16 and out.shape == (total, D) and out.is_contiguous()
+    q = qkv.data_ptr()
+    check(lib().sc_attention_fwd_text(q, q + D * 2, q + 2 * D * 2, ptr(out), ptr(row_off_i32), B, H, int(rows_max), total, 64, 3 * D, D, 0.125,
+                                      _lib.ATTN_TEXT_GENERAL if general else 0, stream()), "sc_attention_fwd_text")
+    return out
+
+
 def unpack_rows(src, row_off_i32, B, T_out, halo=0):
     """src [n, total_rows, D] or [total_rows, D] (packed) -> [n, B, T_out, D] / [B, T_out, D], zeros beyond each utterance's rows; the last `halo`
     rows of every utterance are not copied (the packed engine's receptive-field row)."""
