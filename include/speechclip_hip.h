@@ -375,6 +375,42 @@ int sc_grad_norm(const float* g, int64_t n, float max_norm, void* workspace, flo
 int sc_adam_step(float* p, const float* g, float* m, float* v, int64_t n, const float* clip_coef, float lr, float beta1, float beta2, float eps,
                  float weight_decay, int step, void* stream);
 
+/* ---- Deterministic reductions: the three order-dependent sums of the tail (split-K sc_sgemm, chunked sc_colsum, the 8 waves of
+ * sc_cls_pool_bwd) with ONE writer per element and a stated order, no atomics.  Same arithmetic inside a slice / chunk / wave as the default
+ * entries, same tile shapes and the same split rules, so the default entries' error bounds hold unchanged; only the order in which the
+ * partial sums meet is fixed.  Every "+" and "*" below is one correctly rounded fp32 operation, never contracted into an FMA, so the
+ * chains can be restated bit for bit in fp32 on a host.  Workspaces are caller-owned, must not be shared between streams, and need no
+ * initialisation; their contents after the call are the partials described here.
+ *
+ * sc_sgemm_batched_det / sc_sgemm_det: sc_sgemm_batched / sc_sgemm.  slices = sc_sgemm_det_slices (the split-K rule of sc_sgemm_batched),
+ *   workspace f32 [batch][slices][M][N] = sc_sgemm_det_workspace_bytes = slices * M * N * batch * 4.
+ *   slices == 1: the call IS sc_sgemm_batched (same kernel, same bits); the workspace is not touched and may be NULL.
+ *   slices  > 1: slice s stores p_s = alpha * acc_s (acc_s: the FMA chain over its K range, ascending k) to workspace[b][s]; then
+ *       C = (...((t + p_0) + p_1) + ... ) + p_{slices-1},   t = beta * C (+0 when beta == 0: C is not read), then t = t + bias[n] when bias is given.
+ * sc_colsum_det: sc_colsum.  chunks = sc_colsum_det_chunks (the chunk rule of sc_colsum), workspace f32 [chunks][cols] =
+ *   sc_colsum_det_workspace_bytes = chunks * cols * 4.  chunks == 1: the call IS sc_colsum.  chunks > 1: chunk k stores its sum p_k (four
+ *   row-interleaved partials q_0..q_3, p_k = (q_0 + q_1) + (q_2 + q_3)) to workspace[k]; then out = (...((p_0 + p_1) + p_2) ...) + p_{chunks-1},
+ *   and out = that + old out when accumulate.
+ * sc_cls_pool_bwd_det: sc_cls_pool_bwd, same arguments and outputs.  Wave w of a block owns keys w, w + 8 * nsplit, ... of its key split and
+ *   accumulates du and dalpha over them in ascending key; the block's result is ((w_0 + w_1) + w_2) + ... + w_7 for every element of du and
+ *   dalpha.  dcls_key, ds_ws and pp_ws have one writer in both entries and are bit-identical to sc_cls_pool_bwd's.  The B * nsplit partial
+ *   rows are summed by the caller (sc_colsum_det / sc_sgemm_det for a fixed order). */
+int sc_sgemm_det_slices(int M, int N, int K, int batch);
+int64_t sc_sgemm_det_workspace_bytes(int M, int N, int K, int batch);
+int sc_sgemm_batched_det(int transa, int transb, int M, int N, int K, float alpha, const float* A, int64_t lda, int64_t strideA, const float* B,
+                         int64_t ldb, int64_t strideB, float beta, float* C, int64_t ldc, int64_t strideC, const float* bias, int64_t strideBias,
+                         int batch, void* workspace, int64_t workspace_bytes, void* stream);
+int sc_sgemm_det(int transa, int transb, int M, int N, int K, float alpha, const float* A, int64_t lda, const float* B, int64_t ldb, float beta,
+                 float* C, int64_t ldc, const float* bias, void* workspace, int64_t workspace_bytes, void* stream);
+int sc_colsum_det_chunks(int rows, int cols);
+int64_t sc_colsum_det_workspace_bytes(int rows, int cols);
+int sc_colsum_det(const float* x, int64_t ld, int rows, int cols, float* out, int accumulate, void* workspace, int64_t workspace_bytes,
+                  void* stream);
+int sc_cls_pool_bwd_det(const void* x, int64_t ld_x, const float* cls_tok, const void* hidden, int hidden_f32, int64_t layer_stride, int n_layers,
+                        int normalize, const float* p, const float* dzbar, const float* u, const int32_t* lens, float* ds_ws, float* pp_ws,
+                        float* du, float* dcls_key, float* dalpha, int B, int T, int NQ, int R, int D, int nsplit, float drop_p, uint32_t seed,
+                        void* stream);
+
 /* ---- Fine-tuning HuBERT transformer layers (speech_encoder_plus.py:416-446: `trainable` with `reinit_layers` / `unfreeze_layers`; the feature
  * extractor, positional conv and projections stay frozen as the reference freezes them in those modes).  The dense products of the backward
  * run on sc_gemm_bf16 / sc_gemm_bf16_batched (dX = dY W on transposed weight copies; dW = dY^T X as a split-K batched product over

@@ -168,6 +168,14 @@ def _declare(L):
         "sc_grad_norm_workspace_bytes": ([], c_int64),
         "sc_grad_norm": ([P, L64, F, P, P, P], c_int),
         "sc_adam_step": ([P, P, P, P, L64, P, F, F, F, F, F, I, P], c_int),
+        "sc_sgemm_det_slices": ([I, I, I, I], c_int),
+        "sc_sgemm_det_workspace_bytes": ([I, I, I, I], c_int64),
+        "sc_sgemm_batched_det": ([I, I, I, I, I, F, P, L64, L64, P, L64, L64, F, P, L64, L64, P, L64, I, P, L64, P], c_int),
+        "sc_sgemm_det": ([I, I, I, I, I, F, P, L64, P, L64, F, P, L64, P, P, L64, P], c_int),
+        "sc_colsum_det_chunks": ([I, I], c_int),
+        "sc_colsum_det_workspace_bytes": ([I, I], c_int64),
+        "sc_colsum_det": ([P, L64, I, I, P, I, P, L64, P], c_int),
+        "sc_cls_pool_bwd_det": ([P, L64, P, P, I, L64, I, I, P, P, P, P, P, P, P, P, P, I, I, I, I, I, I, F, U32, P], c_int),
     }
     for name, (args, res) in sigs.items():
         fn = getattr(L, name)   # AttributeError here = header/library mismatch: fail loudly

@@ -23,7 +23,10 @@ __device__ __forceinline__ void load4(const float* __restrict__ p, int n_valid, 
     }
 }
 
-template <bool TA, bool TB>
+// DET (sc_sgemm_batched_det, split_k > 1 only): slice ks stores alpha * acc to its own plane of a workspace that arrives in the C
+// arguments ([batch][nsplit][M][N]: ldc = N, sC = nsplit * M * N) and sgemm_finish_kernel adds the planes in ascending ks.  The DET = false
+// instantiation is the kernel as it was.
+template <bool TA, bool TB, bool DET = false>
 __global__ __launch_bounds__(256) void sgemm_kernel(int M, int N, int K, float alpha, const float* __restrict__ A, int64_t lda, int64_t sA,
                                                     const float* __restrict__ B, int64_t ldb, int64_t sB, float beta, float* __restrict__ C, int64_t ldc,
                                                     int64_t sC, const float* __restrict__ bias, int64_t sBias, int k_per_split, int nsplit, int vec_a, int vec_b) {
@@ -82,6 +85,7 @@ __global__ __launch_bounds__(256) void sgemm_kernel(int M, int N, int K, float a
         }
     }
     const bool split = nsplit > 1;
+    if (DET) C += (int64_t)ks * M * N;
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
         const int m = m0 + ty * 4 + i;
@@ -92,7 +96,9 @@ __global__ __launch_bounds__(256) void sgemm_kernel(int M, int N, int K, float a
             if (n >= N) continue;
             float* c = C + (int64_t)m * ldc + n;
             float v = alpha * acc[i][j];
-            if (split) {
+            if (DET) {
+                *c = v;
+            } else if (split) {
                 atomicAdd(c, v);
             } else {
                 if (bias) v += bias[n];
@@ -112,24 +118,51 @@ __global__ void sgemm_prescale_kernel(float* C, int64_t ldc, int64_t sC, int M, 
         *c = v;
     }
 }
+
+// One writer per element: C = ((beta * C + bias) + p_0) + p_1 + ... in ascending slice, every operation rounded on its own (no FMA), so
+// the chain can be restated exactly in fp32 on the host.  beta = 0 starts from +0 and does not read C.
+__global__ void sgemm_finish_kernel(float* __restrict__ C, int64_t ldc, int64_t sC, int M, int N, float beta, const float* __restrict__ bias, int64_t sBias,
+                                    const float* __restrict__ ws, int nsplit) {
+    const int n = blockIdx.x * blockDim.x + threadIdx.x, m = blockIdx.y, bz = blockIdx.z;
+    if (n < N) {
+        float* c = C + bz * sC + (int64_t)m * ldc + n;
+        const float* p = ws + ((int64_t)bz * nsplit * M + m) * N + n;
+        float v = beta != 0.f ? __fmul_rn(beta, *c) : 0.f;
+        if (bias) v = __fadd_rn(v, bias[bz * sBias + n]);
+        for (int s = 0; s < nsplit; ++s) v = __fadd_rn(v, p[(int64_t)s * M * N]);
+        *c = v;
+    }
+}
+
+// the split-K rule of sc_sgemm_batched and sc_sgemm_batched_det: few output tiles, long reduction: split K so the chip is not idle
+void sgemm_split_rule(int M, int N, int K, int batch, int* split_out, int* k_per_split_out) {
+    const int tiles = ((M + TS - 1) / TS) * ((N + TS - 1) / TS) * batch;
+    int split = 1;
+    if (tiles < 128 && K >= 2048) {
+        split = min(64, max(1, 512 / tiles));
+        while (split > 1 && K / split < 256) --split;
+    }
+    const int k_per_split = ((K + split - 1) / split + KC - 1) / KC * KC;
+    *split_out = (K + k_per_split - 1) / k_per_split;
+    *k_per_split_out = k_per_split;
+}
+
+int sgemm_args_ok(int transa, int transb, int M, int N, int K, const float* A, int64_t lda, const float* B, int64_t ldb, const float* C, int64_t ldc, int batch) {
+    SC_CHECK_ARG(M > 0 && N > 0 && K > 0 && batch > 0, "sc_sgemm: empty problem M=%d N=%d K=%d batch=%d", M, N, K, batch);
+    SC_CHECK_ARG(A && B && C, "sc_sgemm: null operand");
+    SC_CHECK_ARG(lda >= (transa ? M : K) && ldb >= (transb ? K : N) && ldc >= N, "sc_sgemm: leading dimension too small");
+    return 0;
+}
 }  // namespace
 
 // batch > 1: operand b of the batch starts at A + b*strideA etc. (the per-head products of the attention block in ONE launch)
 extern "C" int sc_sgemm_batched(int transa, int transb, int M, int N, int K, float alpha, const float* A, int64_t lda, int64_t strideA,
                                 const float* B, int64_t ldb, int64_t strideB, float beta, float* C, int64_t ldc, int64_t strideC, const float* bias,
                                 int64_t strideBias, int batch, void* stream) {
-    SC_CHECK_ARG(M > 0 && N > 0 && K > 0 && batch > 0, "sc_sgemm: empty problem M=%d N=%d K=%d batch=%d", M, N, K, batch);
-    SC_CHECK_ARG(A && B && C, "sc_sgemm: null operand");
-    SC_CHECK_ARG(lda >= (transa ? M : K) && ldb >= (transb ? K : N) && ldc >= N, "sc_sgemm: leading dimension too small");
+    if (sgemm_args_ok(transa, transb, M, N, K, A, lda, B, ldb, C, ldc, batch)) return -1;
     hipStream_t s = (hipStream_t)stream;
-    const int tiles = ((M + TS - 1) / TS) * ((N + TS - 1) / TS) * batch;
-    int split = 1;
-    if (tiles < 128 && K >= 2048) {               // few output tiles, long reduction: split K so the chip is not idle
-        split = min(64, max(1, 512 / tiles));
-        while (split > 1 && K / split < 256) --split;
-    }
-    int k_per_split = ((K + split - 1) / split + KC - 1) / KC * KC;
-    split = (K + k_per_split - 1) / k_per_split;
+    int split, k_per_split;
+    sgemm_split_rule(M, N, K, batch, &split, &k_per_split);
     SC_CHECK_ARG((int64_t)batch * split <= 65535, "sc_sgemm: batch x split-K = %lld exceeds grid.z", (long long)batch * split);
     if (split > 1) {
         hipLaunchKernelGGL(sgemm_prescale_kernel, dim3((N + 255) / 256, M, batch), dim3(256), 0, s, C, ldc, strideC, M, N, beta, bias, strideBias);
@@ -144,6 +177,50 @@ extern "C" int sc_sgemm_batched(int transa, int transb, int M, int N, int K, flo
 #undef SC_SGEMM_LAUNCH
     SC_CHECK_LAUNCH();
     return 0;
+}
+
+// ---- the same products with a fixed summation order (include/speechclip_hip.h, "Deterministic reductions")
+extern "C" int sc_sgemm_det_slices(int M, int N, int K, int batch) {
+    if (M <= 0 || N <= 0 || K <= 0 || batch <= 0) return 0;
+    int split, k_per_split;
+    sgemm_split_rule(M, N, K, batch, &split, &k_per_split);
+    return split;
+}
+
+extern "C" int64_t sc_sgemm_det_workspace_bytes(int M, int N, int K, int batch) {
+    return (int64_t)sc_sgemm_det_slices(M, N, K, batch) * M * N * batch * 4;
+}
+
+extern "C" int sc_sgemm_batched_det(int transa, int transb, int M, int N, int K, float alpha, const float* A, int64_t lda, int64_t strideA,
+                                    const float* B, int64_t ldb, int64_t strideB, float beta, float* C, int64_t ldc, int64_t strideC, const float* bias,
+                                    int64_t strideBias, int batch, void* workspace, int64_t workspace_bytes, void* stream) {
+    if (sgemm_args_ok(transa, transb, M, N, K, A, lda, B, ldb, C, ldc, batch)) return -1;
+    int split, k_per_split;
+    sgemm_split_rule(M, N, K, batch, &split, &k_per_split);
+    if (split == 1)          // one slice: nothing to order, sc_sgemm_batched's kernel and bits; the workspace is not touched
+        return sc_sgemm_batched(transa, transb, M, N, K, alpha, A, lda, strideA, B, ldb, strideB, beta, C, ldc, strideC, bias, strideBias, batch, stream);
+    SC_CHECK_ARG((int64_t)batch * split <= 65535, "sc_sgemm: batch x split-K = %lld exceeds grid.z", (long long)batch * split);
+    const int64_t need = (int64_t)split * M * N * batch * 4;
+    SC_CHECK_ARG(workspace && workspace_bytes >= need, "sc_sgemm_batched_det: workspace of %lld bytes, %lld needed (sc_sgemm_det_workspace_bytes)",
+                 (long long)workspace_bytes, (long long)need);
+    hipStream_t s = (hipStream_t)stream;
+    float* ws = (float*)workspace;
+    const int vec_a = ((uintptr_t)A % 16 == 0) && lda % 4 == 0 && strideA % 4 == 0;
+    const int vec_b = ((uintptr_t)B % 16 == 0) && ldb % 4 == 0 && strideB % 4 == 0;
+    dim3 grid((N + TS - 1) / TS, (M + TS - 1) / TS, split * batch);
+#define SC_SGEMM_LAUNCH(TA, TB) hipLaunchKernelGGL((sgemm_kernel<TA, TB, true>), grid, dim3(256), 0, s, M, N, K, alpha, A, lda, strideA, B, ldb, strideB, 0.f, ws, (int64_t)N, (int64_t)split * M * N, (const float*)nullptr, (int64_t)0, k_per_split, split, vec_a, vec_b)
+    if (transa) { if (transb) SC_SGEMM_LAUNCH(true, true); else SC_SGEMM_LAUNCH(true, false); }
+    else        { if (transb) SC_SGEMM_LAUNCH(false, true); else SC_SGEMM_LAUNCH(false, false); }
+#undef SC_SGEMM_LAUNCH
+    SC_CHECK_LAUNCH();
+    hipLaunchKernelGGL(sgemm_finish_kernel, dim3((N + 255) / 256, M, batch), dim3(256), 0, s, C, ldc, strideC, M, N, beta, bias, strideBias, ws, split);
+    SC_CHECK_LAUNCH();
+    return 0;
+}
+
+extern "C" int sc_sgemm_det(int transa, int transb, int M, int N, int K, float alpha, const float* A, int64_t lda, const float* B, int64_t ldb,
+                            float beta, float* C, int64_t ldc, const float* bias, void* workspace, int64_t workspace_bytes, void* stream) {
+    return sc_sgemm_batched_det(transa, transb, M, N, K, alpha, A, lda, 0, B, ldb, 0, beta, C, ldc, 0, bias, 0, 1, workspace, workspace_bytes, stream);
 }
 
 extern "C" int sc_sgemm(int transa, int transb, int M, int N, int K, float alpha, const float* A, int64_t lda, const float* B, int64_t ldb,

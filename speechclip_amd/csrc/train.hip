@@ -178,7 +178,11 @@ __global__ __launch_bounds__(256) void cls_pool_bwd_scores_kernel(const bf16_t* 
 // Grid (B, S): the keys of an utterance are split over S blocks, each writing its own partial row -- every consumer sums these
 // outputs over b anyway (colsum / sc_mix_softmax_bwd), so the split costs nothing and gives the memory system 4 x S waves per
 // utterance instead of 4.  Per-wave partials meet in ONE [8][D] LDS buffer through ds_add (24 KiB: several blocks per CU).
-template <int DCH, int NL>   // NL: compile-time bound of n_layers (16 or 32): per-layer partial sums stay in registers, loads of several layers overlap
+// DET (sc_cls_pool_bwd_det): the same pass with the 8 waves' partials added in wave order 0..7 by ONE thread per element.  Eight per-wave copies
+// of red[8][D] do not fit, so du is reduced in groups of 3 rows r: after the frame loop dzbar / u are dead and their 16 D floats plus red's 8 D
+// hold [3 rows][8 waves][D]; every wave stores its rows of the group, a barrier, then thread i adds the 8 waves' values of element i in
+// ascending wave and writes du.  dalpha goes through [wave][32] in the same way.  DET = false is the kernel as it was.
+template <int DCH, int NL, bool DET = false>   // NL: compile-time bound of n_layers (16 or 32): per-layer partial sums stay in registers, loads of several layers overlap
 __global__ __launch_bounds__(512) void cls_pool_bwd_frames_kernel(const bf16_t* __restrict__ x, int64_t ld_x, const float* __restrict__ cls_tok,
                                                                   const void* __restrict__ hidden, int hidden_f32, int64_t layer_stride, int n_layers, int normalize, float eps,
                                                                   const float* __restrict__ pp, const float* __restrict__ ds, const float* __restrict__ dzbar,
@@ -191,7 +195,7 @@ __global__ __launch_bounds__(512) void cls_pool_bwd_frames_kernel(const bf16_t* 
     float* sg = (float*)smem;                 // [8][D] dzbar_r
     float* su = sg + 8 * D;                   // [8][D] u_r
     float* red = su + 8 * D;                  // [8][D] du accumulators (ds_add from the 8 waves)
-    float* sda = red + 8 * D;                 // [32]   dalpha
+    float* sda = red + 8 * D;                 // [32]   dalpha ([8 waves][32] under DET)
     const int NW = 8;
     const int b = blockIdx.x, S = gridDim.y, sp = blockIdx.y, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int64_t orow = (int64_t)b * S + sp;  // output row of this block
@@ -296,6 +300,47 @@ __global__ __launch_bounds__(512) void cls_pool_bwd_frames_kernel(const bf16_t* 
             }
         }
     }
+    if (DET) {
+        if (hidden) {
+#pragma unroll
+            for (int n = 0; n < NL; ++n) {
+                if (n >= n_layers) break;
+                const float t = wave_sum(da[n]);
+                if (lane == 0) sda[wave * 32 + n] = t;
+            }
+        }
+        float* part = sg;                     // [3][8 waves][D] over sg, su and red: all three are dead once every wave has left the frame loop
+#pragma unroll
+        for (int g = 0; g < 3; ++g) {
+            if (g * 3 >= R) break;
+            __syncthreads();                  // g = 0: the frame loop's reads of sg / su are over;  g > 0: the sums of the group before are taken
+#pragma unroll
+            for (int j = 0; j < 3; ++j) {
+                const int r = g * 3 + j;
+                if (r < 8 && r < R) {
+#pragma unroll
+                    for (int c = 0; c < DCH; ++c)
+                        if (c * 256 + lane * 4 < D)
+                            *(f32x4_t*)(part + (j * NW + wave) * D + c * 256 + lane * 4) =
+                                (f32x4_t){dua[r < 8 ? r : 0][c][0], dua[r < 8 ? r : 0][c][1], dua[r < 8 ? r : 0][c][2], dua[r < 8 ? r : 0][c][3]};
+                }
+            }
+            __syncthreads();
+            const int nr = min(3, R - g * 3);
+            for (int i = tid; i < nr * D; i += 512) {
+                const int j = i / D, d = i - j * D;
+                float t = part[(j * NW) * D + d];
+                for (int w = 1; w < NW; ++w) t += part[(j * NW + w) * D + d];
+                du[orow * R * D + (int64_t)(g * 3 + j) * D + d] = t;
+            }
+        }
+        if (hidden && tid < n_layers) {       // (sda was written before the barriers above)
+            float t = sda[tid];
+            for (int w = 1; w < NW; ++w) t += sda[w * 32 + tid];
+            dalpha[orow * n_layers + tid] = t;
+        }
+        return;
+    }
     if (hidden) {
 #pragma unroll
         for (int n = 0; n < NL; ++n) {
@@ -397,7 +442,9 @@ __global__ void gelu_fwd_kernel(const float* __restrict__ z, float* __restrict__
     y[i] = 0.5f * v * (1.0f + erff(v * 0.70710678118654752f));
 }
 // out[c] (+)= sum_r x[r, c].  Grid (column blocks of 64, row chunks): tall inputs are reduced by several blocks per column block through
-// atomics on a pre-zeroed / pre-existing `out`.
+// atomics on a pre-zeroed / pre-existing `out`.  DET (sc_colsum_det, more than one chunk only): chunk y stores its sum to row y of a
+// workspace that arrives as `out` ([chunks][cols]) and colsum_finish_kernel adds the rows in ascending y; DET = false is the kernel as it was.
+template <bool DET = false>
 __global__ void colsum_kernel(const float* __restrict__ x, int64_t ld, int rows, int cols, float* __restrict__ out, int accumulate, int rows_per_block) {
     const int c = blockIdx.x * 64 + (threadIdx.x & 63);
     const int sub = threadIdx.x >> 6;                       // 4 row-interleaved partial sums per column
@@ -410,9 +457,18 @@ __global__ void colsum_kernel(const float* __restrict__ x, int64_t ld, int rows,
     __syncthreads();
     if (sub == 0 && c < cols) {
         s = (part[0][threadIdx.x] + part[1][threadIdx.x]) + (part[2][threadIdx.x] + part[3][threadIdx.x]);
-        if (gridDim.y > 1) atomicAdd(out + c, s);
+        if (DET) out[(int64_t)blockIdx.y * cols + c] = s;
+        else if (gridDim.y > 1) atomicAdd(out + c, s);
         else out[c] = accumulate ? out[c] + s : s;
     }
+}
+// out[c] = (((p_0 + p_1) + ...) + p_last) (+ old out[c] when accumulate, added last): one writer per column, no FMA to contract
+__global__ void colsum_finish_kernel(const float* __restrict__ ws, int chunks, int cols, float* __restrict__ out, int accumulate) {
+    const int c = blockIdx.x * blockDim.x + threadIdx.x;
+    if (c >= cols) return;
+    float v = ws[c];
+    for (int k = 1; k < chunks; ++k) v = __fadd_rn(v, ws[(int64_t)k * cols + c]);
+    out[c] = accumulate ? __fadd_rn(v, out[c]) : v;
 }
 // y = x / |x|:  dx = (dy - y (y . dy)) / |x|
 __global__ __launch_bounds__(256) void l2norm_bwd_kernel(const float* __restrict__ x, const float* __restrict__ dy, float* __restrict__ dx, int rows, int D) {
@@ -611,7 +667,8 @@ extern "C" int sc_cls_pool_train_fwd(const void* x, int64_t ld_x, const float* c
     return 0;
 }
 
-extern "C" int sc_cls_pool_bwd(const void* x, int64_t ld_x, const float* cls_tok, const void* hidden, int hidden_f32, int64_t layer_stride,
+template <bool DET>
+static int cls_pool_bwd_launch(const void* x, int64_t ld_x, const float* cls_tok, const void* hidden, int hidden_f32, int64_t layer_stride,
                                int n_layers, int normalize, const float* p, const float* dzbar, const float* u, const int32_t* lens, float* ds_ws,
                                float* pp_ws, float* du, float* dcls_key, float* dalpha, int B, int T, int NQ, int R, int D, int nsplit,
                                float drop_p, uint32_t seed, void* stream) {
@@ -624,12 +681,12 @@ extern "C" int sc_cls_pool_bwd(const void* x, int64_t ld_x, const float* cls_tok
     POOL_DISPATCH(cls_pool_bwd_scores_kernel, lds_a, (const bf16_t*)x, ld_x, cls_tok, p, dzbar, lens, ds_ws, pp_ws, T, NQ, R, D, seed,
                   drop_thresh(drop_p), 1.0f / (1.0f - drop_p));
     SC_CHECK_LAUNCH();
-    const int lds_b = (3 * 8 * D + 32) * 4;
+    const int lds_b = (3 * 8 * D + (DET ? 8 * 32 : 32)) * 4;
     const dim3 grid_b(B, nsplit);
 #define FRAMES_LAUNCH(DCH_) do { if (n_layers <= 16) FRAMES_LAUNCH2(DCH_, 16); else FRAMES_LAUNCH2(DCH_, 32); } while (0)
 #define FRAMES_LAUNCH2(DCH_, NL_) do {                                                                                                                \
-    (void)hipFuncSetAttribute((const void*)cls_pool_bwd_frames_kernel<DCH_, NL_>, hipFuncAttributeMaxDynamicSharedMemorySize, lds_b);                   \
-    hipLaunchKernelGGL((cls_pool_bwd_frames_kernel<DCH_, NL_>), grid_b, dim3(512), lds_b, s, (const bf16_t*)x, ld_x, cls_tok, (const void*)(n_layers ? hidden : nullptr), \
+    (void)hipFuncSetAttribute((const void*)cls_pool_bwd_frames_kernel<DCH_, NL_, DET>, hipFuncAttributeMaxDynamicSharedMemorySize, lds_b);              \
+    hipLaunchKernelGGL((cls_pool_bwd_frames_kernel<DCH_, NL_, DET>), grid_b, dim3(512), lds_b, s, (const bf16_t*)x, ld_x, cls_tok, (const void*)(n_layers ? hidden : nullptr), \
                        hidden_f32, layer_stride, n_layers, normalize, 1e-5f, pp_ws, ds_ws, dzbar, u, lens, du, dcls_key, dalpha, T, NQ, R, D); } while (0)
     if (D <= 256) FRAMES_LAUNCH(1);
     else if (D <= 512) FRAMES_LAUNCH(2);
@@ -639,6 +696,23 @@ extern "C" int sc_cls_pool_bwd(const void* x, int64_t ld_x, const float* cls_tok
 #undef FRAMES_LAUNCH2
     SC_CHECK_LAUNCH();
     return 0;
+}
+
+extern "C" int sc_cls_pool_bwd(const void* x, int64_t ld_x, const float* cls_tok, const void* hidden, int hidden_f32, int64_t layer_stride,
+                               int n_layers, int normalize, const float* p, const float* dzbar, const float* u, const int32_t* lens, float* ds_ws,
+                               float* pp_ws, float* du, float* dcls_key, float* dalpha, int B, int T, int NQ, int R, int D, int nsplit,
+                               float drop_p, uint32_t seed, void* stream) {
+    return cls_pool_bwd_launch<false>(x, ld_x, cls_tok, hidden, hidden_f32, layer_stride, n_layers, normalize, p, dzbar, u, lens, ds_ws, pp_ws, du, dcls_key,
+                                      dalpha, B, T, NQ, R, D, nsplit, drop_p, seed, stream);
+}
+
+// sc_cls_pool_bwd with the block's 8 waves summed in wave order (include/speechclip_hip.h, "Deterministic reductions")
+extern "C" int sc_cls_pool_bwd_det(const void* x, int64_t ld_x, const float* cls_tok, const void* hidden, int hidden_f32, int64_t layer_stride,
+                                   int n_layers, int normalize, const float* p, const float* dzbar, const float* u, const int32_t* lens, float* ds_ws,
+                                   float* pp_ws, float* du, float* dcls_key, float* dalpha, int B, int T, int NQ, int R, int D, int nsplit,
+                                   float drop_p, uint32_t seed, void* stream) {
+    return cls_pool_bwd_launch<true>(x, ld_x, cls_tok, hidden, hidden_f32, layer_stride, n_layers, normalize, p, dzbar, u, lens, ds_ws, pp_ws, du, dcls_key,
+                                     dalpha, B, T, NQ, R, D, nsplit, drop_p, seed, stream);
 }
 
 extern "C" int sc_layernorm_bwd(const float* x, const float* dy, const float* gamma, float* dx, float* dgamma, float* dbeta, float* stats_ws,
@@ -664,16 +738,50 @@ extern "C" int sc_gelu_f32(const float* z, float* y_or_dh, int64_t n, int backwa
     return 0;
 }
 
-extern "C" int sc_colsum(const float* x, int64_t ld, int rows, int cols, float* out, int accumulate, void* stream) {
-    if (rows <= 0 || cols <= 0) return 0;
-    hipStream_t s = (hipStream_t)stream;
+// the chunk rule of sc_colsum and sc_colsum_det -> row chunks (rows per chunk in *rpb_out)
+static int colsum_chunk_rule(int rows, int cols, int* rpb_out) {
     const int cb = (cols + 63) / 64;
     int chunks = 1;
     if (rows >= 256 && cb < 512) chunks = min((rows + 63) / 64, max(1, 1024 / cb));
     const int rpb = (rows + chunks - 1) / chunks;
-    chunks = (rows + rpb - 1) / rpb;
+    *rpb_out = rpb;
+    return (rows + rpb - 1) / rpb;
+}
+
+extern "C" int sc_colsum(const float* x, int64_t ld, int rows, int cols, float* out, int accumulate, void* stream) {
+    if (rows <= 0 || cols <= 0) return 0;
+    hipStream_t s = (hipStream_t)stream;
+    const int cb = (cols + 63) / 64;
+    int rpb;
+    const int chunks = colsum_chunk_rule(rows, cols, &rpb);
     if (chunks > 1 && !accumulate) { if (hipMemsetAsync(out, 0, (size_t)cols * 4, s) != hipSuccess) { sc_set_error("sc_colsum: memset failed"); return -2; } }
-    hipLaunchKernelGGL(colsum_kernel, dim3(cb, chunks), dim3(256), 0, s, x, ld, rows, cols, out, accumulate, rpb);
+    hipLaunchKernelGGL(colsum_kernel<false>, dim3(cb, chunks), dim3(256), 0, s, x, ld, rows, cols, out, accumulate, rpb);
+    SC_CHECK_LAUNCH();
+    return 0;
+}
+
+// ---- the same sums with a fixed order (include/speechclip_hip.h, "Deterministic reductions")
+extern "C" int sc_colsum_det_chunks(int rows, int cols) {
+    if (rows <= 0 || cols <= 0) return 0;
+    int rpb;
+    return colsum_chunk_rule(rows, cols, &rpb);
+}
+
+extern "C" int64_t sc_colsum_det_workspace_bytes(int rows, int cols) { return (int64_t)sc_colsum_det_chunks(rows, cols) * cols * 4; }
+
+extern "C" int sc_colsum_det(const float* x, int64_t ld, int rows, int cols, float* out, int accumulate, void* workspace, int64_t workspace_bytes,
+                             void* stream) {
+    if (rows <= 0 || cols <= 0) return 0;
+    int rpb;
+    const int chunks = colsum_chunk_rule(rows, cols, &rpb);
+    if (chunks == 1) return sc_colsum(x, ld, rows, cols, out, accumulate, stream);          // one chunk: sc_colsum's kernel and bits, no workspace
+    const int64_t need = (int64_t)chunks * cols * 4;
+    SC_CHECK_ARG(workspace && workspace_bytes >= need, "sc_colsum_det: workspace of %lld bytes, %lld needed (sc_colsum_det_workspace_bytes)",
+                 (long long)workspace_bytes, (long long)need);
+    hipStream_t s = (hipStream_t)stream;
+    hipLaunchKernelGGL(colsum_kernel<true>, dim3((cols + 63) / 64, chunks), dim3(256), 0, s, x, ld, rows, cols, (float*)workspace, 0, rpb);
+    SC_CHECK_LAUNCH();
+    hipLaunchKernelGGL(colsum_finish_kernel, dim3((cols + 255) / 256), dim3(256), 0, s, (const float*)workspace, chunks, cols, out, accumulate);
     SC_CHECK_LAUNCH();
     return 0;
 }

@@ -758,6 +758,55 @@ def _f32c(*ts):
             assert t.is_cuda and t.dtype == torch.float32 and t.is_contiguous(), (t.dtype, t.is_contiguous())
 
 
+# Deterministic mode ('Reproducibility'): the three order-dependent reductions of a training step -- split-K sc_sgemm, chunked
+# sc_colsum and the 8 waves of sc_cls_pool_bwd -- go through their fixed-order entries (sc_*_det).  Opt in with SC_DETERMINISTIC=1 (read once,
+# here), set_deterministic(True), or torch.use_deterministic_algorithms(True) (read at every call, never set).  The choice is made in sgemm /
+# sgemm_batched / colsum / cls_pool_bwd below and nowhere else.  Workspaces are allocated per call from torch's caching allocator on the
+# current stream, so two streams never share one.
+def _env_flag(value) -> bool:
+    return str(value or "").strip().lower() in ("1", "true", "on", "yes")
+
+
+_DETERMINISTIC = [_env_flag(_os.environ.get("SC_DETERMINISTIC"))]
+_DET_COUNTERS = {"sgemm_split": 0, "colsum_chunks": 0, "cls_pool_bwd": 0}
+
+
+def set_deterministic(enabled: bool) -> None:
+    _DETERMINISTIC[0] = bool(enabled)
+
+
+def deterministic() -> bool:
+    return _DETERMINISTIC[0] or torch.are_deterministic_algorithms_enabled()
+
+
+def det_counters(reset: bool = False) -> dict:
+    """Calls since the last reset that took the deterministic split-K path (more than one slice), chunk path (more than one chunk) and
+    pooling-backward path."""
+    out = dict(_DET_COUNTERS)
+    if reset:
+        for k in _DET_COUNTERS:
+            _DET_COUNTERS[k] = 0
+    return out
+
+
+def _det_workspace(nbytes, dev):
+    return torch.empty(nbytes // 4, device=dev, dtype=torch.float32)
+
+
+def _sgemm_det(transa, transb, M, N, K, alpha, a, lda, stride_a, b, ldb, stride_b, beta, out, ldc, stride_c, bias, stride_bias, batch) -> bool:
+    """The product through sc_sgemm_batched_det when the mode is on and the split-K rule gives more than one slice (one slice has nothing to
+    order: the caller's default entry runs).  -> whether it ran."""
+    L = lib()
+    if not deterministic() or L.sc_sgemm_det_slices(M, N, K, batch) <= 1:
+        return False
+    nbytes = L.sc_sgemm_det_workspace_bytes(M, N, K, batch)
+    ws = _det_workspace(nbytes, out.device)
+    _DET_COUNTERS["sgemm_split"] += 1
+    check(L.sc_sgemm_batched_det(int(transa), int(transb), M, N, K, alpha, ptr(a), lda, stride_a, ptr(b), ldb, stride_b, beta, ptr(out), ldc, stride_c,
+                                 ptr(bias), stride_bias, batch, ptr(ws), nbytes, stream()), "sc_sgemm_batched_det")
+    return True
+
+
 def sgemm(a, b, transa=False, transb=False, alpha=1.0, beta=0.0, out=None, bias=None):
     """out[M,N] = alpha * op(a) @ op(b) + beta * out (+ bias[N]).  fp32, 2-D row-major tensors (last stride 1).
     transa: a stored [K,M]; transb: b stored [N,K] (nn.Linear weight layout)."""
@@ -770,6 +819,8 @@ def sgemm(a, b, transa=False, transb=False, alpha=1.0, beta=0.0, out=None, bias=
         assert beta == 0.0
         out = torch.empty(M, N, device=a.device, dtype=torch.float32)
     assert out.shape == (M, N) and out.dtype == torch.float32 and out.stride(1) == 1
+    if _sgemm_det(transa, transb, M, N, K, alpha, a, a.stride(0), 0, b, b.stride(0), 0, beta, out, out.stride(0), 0, bias, 0, 1):
+        return out
     check(lib().sc_sgemm(int(transa), int(transb), M, N, K, alpha, ptr(a), a.stride(0), ptr(b), b.stride(0), beta, ptr(out), out.stride(0),
                          ptr(bias), stream()), "sc_sgemm")
     return out
@@ -781,6 +832,8 @@ def sgemm_batched(M, N, K, a, lda, stride_a, b, ldb, stride_b, out, ldc, stride_
     per-head products of the attention block in one launch.  a / b / out / bias are tensors (or views) whose data_ptr is operand 0."""
     _need_cuda(a, b, out)
     assert a.dtype == torch.float32 and b.dtype == torch.float32 and out.dtype == torch.float32
+    if _sgemm_det(transa, transb, M, N, K, alpha, a, lda, stride_a, b, ldb, stride_b, beta, out, ldc, stride_c, bias, stride_bias, batch):
+        return out
     check(lib().sc_sgemm_batched(int(transa), int(transb), M, N, K, alpha, ptr(a), lda, stride_a, ptr(b), ldb, stride_b, beta, ptr(out), ldc, stride_c,
                                  ptr(bias), stride_bias, batch, stream()), "sc_sgemm_batched")
     return out
@@ -814,9 +867,13 @@ def cls_pool_bwd(x_rows, cls_tok, hidden, p, dzbar, u, lens_i32, B, T, NQ, R, D,
     du = torch.empty(B * nsplit, R, D, device=dev, dtype=torch.float32)
     dck = torch.empty(B * nsplit, NQ, D, device=dev, dtype=torch.float32)
     dalpha = torch.empty(B * nsplit, n, device=dev, dtype=torch.float32) if n else None
-    check(lib().sc_cls_pool_bwd(ptr(x_rows), x_rows.stride(0), ptr(cls_tok), ptr(hidden), int(n > 0 and hidden.dtype == torch.float32), hidden.stride(0) if n else 0, n,
-                                int(normalize), ptr(p), ptr(dzbar), ptr(u), ptr(lens_i32), ptr(ds), ptr(pp), ptr(du), ptr(dck), ptr(dalpha), B, T, NQ, R, D,
-                                int(nsplit), float(drop_p), int(seed) & 0xFFFFFFFF, stream()), "sc_cls_pool_bwd")
+    det = deterministic()
+    if det:
+        _DET_COUNTERS["cls_pool_bwd"] += 1
+    entry = lib().sc_cls_pool_bwd_det if det else lib().sc_cls_pool_bwd
+    check(entry(ptr(x_rows), x_rows.stride(0), ptr(cls_tok), ptr(hidden), int(n > 0 and hidden.dtype == torch.float32), hidden.stride(0) if n else 0, n,
+                int(normalize), ptr(p), ptr(dzbar), ptr(u), ptr(lens_i32), ptr(ds), ptr(pp), ptr(du), ptr(dck), ptr(dalpha), B, T, NQ, R, D,
+                int(nsplit), float(drop_p), int(seed) & 0xFFFFFFFF, stream()), "sc_cls_pool_bwd_det" if det else "sc_cls_pool_bwd")
     if return_ws:          # (ds, pp): score gradients and post-dropout probabilities [B,R,NQ+T], what sc_cls_pool_dz needs
         return du, dck, dalpha, ds, pp
     return du, dck, dalpha
@@ -856,6 +913,12 @@ def colsum(x, out=None, accumulate=False):
     if out is None:
         out = torch.empty(cols, device=x.device, dtype=torch.float32)
         accumulate = False
+    if deterministic() and lib().sc_colsum_det_chunks(rows, cols) > 1:
+        nbytes = lib().sc_colsum_det_workspace_bytes(rows, cols)
+        ws = _det_workspace(nbytes, x.device)
+        _DET_COUNTERS["colsum_chunks"] += 1
+        check(lib().sc_colsum_det(ptr(x), x.stride(0), rows, cols, ptr(out), int(accumulate), ptr(ws), nbytes, stream()), "sc_colsum_det")
+        return out
     check(lib().sc_colsum(ptr(x), x.stride(0), rows, cols, ptr(out), int(accumulate), stream()), "sc_colsum")
     return out
 
