@@ -121,6 +121,8 @@ def _declare(L):
         "sc_vit_embed_bwd_workspace_bytes": ([I, I, I], c_int64),
         "sc_vit_embed_bwd": ([P, P, P, P, P, P, P, P, P, P, I, I, I, F, P], c_int),
         "sc_image_normalize_u8": ([P, P, I, I, I, P, P, P], c_int),
+        "sc_image_prep_workspace_bytes": ([P, I, I], c_int64),
+        "sc_image_prep_u8": ([P, L64, P, P, P, P, P, P, L64, I, I, P, P, P, L64, P, P, P], c_int),
         "sc_vit_patchify": ([P, P, I, I, I, I, P], c_int),
         "sc_vit_embed": ([P, P, P, P, P, P, I, I, I, F, P], c_int),
         "sc_infonce_workspace_bytes": ([I], c_int64),

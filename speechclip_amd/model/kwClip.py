@@ -15,6 +15,7 @@ import logging
 import os
 from typing import List, Tuple, Union
 
+import numpy as np
 import torch
 from torch import nn
 
@@ -71,7 +72,11 @@ class KWClipBase(BaseLightningModel):
     def forward_image(self, images: Union[list, torch.Tensor]) -> torch.Tensor:
         if isinstance(images, list):          # kwClip.py:517-518: paths -> ClipModel.prep_image (PIL + CLIP `_transform`) on the model's device
             self.clip.update_device(self.device)
-            images = self.clip.prep_image(images)
+            # beyond the reference: a list of decoded frames (uint8 [h, w, 3] / [h, w] arrays or tensors, sizes may differ) -> ClipModel.prep_image_arrays
+            is_frame = [isinstance(im, (np.ndarray, torch.Tensor)) for im in images]
+            if any(is_frame) and not all(is_frame):
+                raise TypeError("forward_image takes a list of paths or a list of decoded uint8 images, not a mix of both")
+            images = self.clip.prep_image_arrays(images) if images and all(is_frame) else self.clip.prep_image(images)
         elif isinstance(images, torch.Tensor):
             if images.dim() != 4 or images.shape[1] != 3:
                 raise ValueError(f"Incorrect image tensor shape {images.shape}")

@@ -21,6 +21,10 @@ SOT_ID, EOT_ID = 49406, 49407
 # the padded one in 3 of 3 interleaved passes (5000 captions of 6 .. 30 rows and one of 77, ViT-B/32: 10.5 ms against 41.5 ms, profiles/text_tower_bench.txt).
 # False would keep `auto` on the padded path; SC_TEXT_PACK=1 / 0 decide regardless.
 _TEXT_PACK_AUTO = True
+# What SC_IMAGE_PREP=auto does for a model on a GPU: True = resize + centre crop on the device (sc_image_prep_u8).  tools/image_prep_bench.py measured the device
+# arm faster than the PIL arm in 3 of 3 interleaved passes on both legs (256 images of 500 x 375 / 375 x 500: PNG files 664 ms against 898 ms per call, decoded
+# arrays 10.5 ms against 301 ms; profiles/image_prep_bench.txt).  The two arms give equal bits; SC_IMAGE_PREP=host / device decide regardless.
+_IMAGE_PREP_AUTO_DEVICE = True
 
 
 class _IdDecoder(dict):
@@ -120,9 +124,36 @@ class ClipModel(nn.Module):
 
     def prep_image(self, paths: list) -> torch.Tensor:
         """clip_official.py:151-164: image files -> pre-processed tensor [B, 3, H, W] on self.device.  PIL open + bicubic resize + centre crop on the
-        host (data/image_transforms.py), then the batch goes to the device as uint8 and is scaled / normalised there (sc_image_normalize_u8)."""
-        from ..data.image_transforms import load_images_u8, normalize_u8
-        return normalize_u8(load_images_u8(paths, self.model.cfg.image_resolution), self.device)
+        host (data/image_transforms.py), then the batch goes to the device as uint8 and is scaled / normalised there (sc_image_normalize_u8).
+        SC_IMAGE_PREP (read at every call) chooses where the geometry runs: `host` = the PIL path above; `device` = decode only on the host
+        (load_images_raw), resize + crop + normalise on the device (ops.image_prep) when the model lives on a GPU, the host path for a CPU model; `auto`
+        (the default) = `device`, which is what the measurement decided (faster in 3 of 3 passes on files and on decoded arrays: README,
+        profiles/image_prep_bench.txt).  The two paths give equal bits, so the choice cannot change a result."""
+        from ..data.image_transforms import load_images_raw, load_images_u8, normalize_u8
+        n_px = self.model.cfg.image_resolution
+        if self._image_prep_on_device():
+            return self.prep_image_arrays(load_images_raw(paths, n_px))
+        return normalize_u8(load_images_u8(paths, n_px), self.device)
+
+    def _image_prep_on_device(self) -> bool:
+        mode = os.environ.get("SC_IMAGE_PREP", "auto")
+        if mode not in ("host", "device", "auto"):
+            raise ValueError(f"SC_IMAGE_PREP={mode!r}: expected host, device or auto")
+        return (mode == "device" or (mode == "auto" and _IMAGE_PREP_AUTO_DEVICE)) and torch.device(self.device).type == "cuda"
+
+    def prep_image_arrays(self, images: list) -> torch.Tensor:
+        """Decoded frames (uint8 [h, w, 3] RGB or [h, w] L arrays / host tensors, sizes may differ: a DataLoader worker's arrays, video frames) ->
+        pre-processed tensor [B, 3, n_px, n_px] on self.device, equal bit for bit to prep_image of the same pictures.  SC_IMAGE_PREP chooses as in
+        prep_image: the geometry on the device (ops.image_prep), or PIL on the arrays and the normalisation on the device."""
+        from ..data.image_transforms import as_u8_image, clip_resize_center_crop_u8, normalize_u8
+        n_px = self.model.cfg.image_resolution
+        if self._image_prep_on_device():
+            from .. import ops
+            with torch.cuda.device(torch.device(self.device)):          # "cuda" without an index (the reference's constructor form) = the current device
+                return ops.image_prep(images, n_px)
+        from PIL import Image
+        crops = [clip_resize_center_crop_u8(Image.fromarray(as_u8_image(im)), n_px) for im in images]
+        return normalize_u8(torch.from_numpy(np.stack(crops)) if crops else torch.empty(0, n_px, n_px, 3, dtype=torch.uint8), self.device)
 
     def encode_image(self, image: torch.Tensor) -> torch.Tensor:
         if self.image_encoder_trainable and torch.is_grad_enabled():

@@ -1216,6 +1216,70 @@ def image_normalize_u8(u8, mean=CLIP_MEAN, std=CLIP_STD):
     return out
 
 
+def image_prep(images, n_px, mean=CLIP_MEAN, std=CLIP_STD, return_u8=False):
+    """CLIP's whole `_transform` on the current device (sc_image_prep_u8): a list of decoded uint8 host images ([h, w, 3] RGB or [h, w] L, arrays or tensors,
+    every image its own size, as data.image_transforms.load_images_raw returns them) -> f32 [B, 3, n_px, n_px]; with return_u8 also the uint8
+    [B, n_px, n_px, 3] crop, which equals PIL's bicubic resize + centre crop on every byte.  The plans (cached per size) and the bytes go into ONE pinned buffer,
+    cross PCIe in one non-blocking copy, and one library call on the current stream does the rest; the workspace comes from torch's allocator on that stream."""
+    return _image_prep(images, n_px, mean, std, return_u8)
+
+
+def _image_prep(images, n_px, mean=CLIP_MEAN, std=CLIP_STD, return_u8=False, device=None, out=None, out_u8=None, workspace=None, pad_bytes=0, plans=None):
+    """image_prep with the knobs the tests need: device (any spelling of a GPU, default the current one), out / out_u8 / workspace = caller-owned buffers to
+    write into (contiguous, right dtype and size; the tests put them between sentinel guards), pad_bytes / plans: see plan_image_batch."""
+    import ctypes
+    import numpy as np
+    from .data.image_transforms import plan_image_batch
+    if not torch.cuda.is_available():
+        raise _lib.SpeechClipHipError("speechclip_amd ops need a GPU: image_prep has no CPU fallback (the host path is data.image_transforms.load_images_u8)")
+    dev = torch.device("cuda") if device is None else torch.device(device)
+    if dev.type != "cuda":
+        raise _lib.SpeechClipHipError("speechclip_amd ops need device tensors (no CPU fallback)")
+    if dev.index is None:          # "cuda" -> the current device WITH its index: the tensors allocated below report an indexed device
+        dev = torch.device("cuda", torch.cuda.current_device())
+    n = int(n_px)
+    plan = plan_image_batch(images, n, pad_bytes=pad_bytes, plans=plans)
+    B = len(plan.images)
+    # one pinned buffer: offsets | geom | tables | (16-byte aligned) pixels.  A fresh pinned tensor per call: torch's host allocator does not hand the block
+    # out again before the copy below has finished.
+    n_off, n_geom, n_tab = plan.offsets.nbytes, plan.geom.nbytes, plan.tables.nbytes
+    head = (n_off + n_geom + n_tab + 15) // 16 * 16
+    host = torch.empty(max(head + plan.packed_bytes, 16), dtype=torch.uint8, pin_memory=True)
+    hb = host.numpy()
+    hb[:n_off] = plan.offsets.reshape(-1).view(np.uint8)
+    hb[n_off:n_off + n_geom] = plan.geom.reshape(-1).view(np.uint8)
+    hb[n_off + n_geom:n_off + n_geom + n_tab] = plan.tables.view(np.uint8)
+    if pad_bytes:
+        hb[head:] = 255
+    for b, im in enumerate(plan.images):
+        o = head + int(plan.offsets[0, b])
+        hb[o:o + im.size] = im.reshape(-1)
+    with torch.cuda.device(dev):
+        d = host.to(dev, non_blocking=True)
+        if out is None:
+            out = torch.empty(B, 3, n, n, device=dev, dtype=torch.float32)
+        if out_u8 is None and return_u8:
+            out_u8 = torch.empty(B, n, n, 3, device=dev, dtype=torch.uint8)
+        if workspace is None:
+            workspace = torch.empty(max(plan.workspace_bytes, 1), device=dev, dtype=torch.uint8)
+        for t, shape, dt in ((out, (B, 3, n, n), torch.float32), (out_u8, (B, n, n, 3), torch.uint8)):
+            if t is not None and not (t.is_cuda and t.device == dev and t.dtype == dt and tuple(t.shape) == shape and t.is_contiguous()):
+                raise ValueError(f"image_prep: output buffer must be a contiguous {dt} {shape} tensor on {dev}")
+        if not (workspace.device == dev and workspace.dtype == torch.uint8 and workspace.is_contiguous()):
+            raise ValueError(f"image_prep: workspace must be a contiguous uint8 tensor on {dev}")
+        if B == 0:
+            return (out, out_u8) if return_u8 else out
+        m = (ctypes.c_float * 3)(*[float(x) for x in mean])
+        sd = (ctypes.c_float * 3)(*[float(x) for x in std])
+        hp, dp = host.data_ptr(), d.data_ptr()
+        has_tab = n_tab > 0
+        with _HbmSpan("image_prep", plan.packed_bytes + 2 * plan.workspace_bytes + B * n * n * (12 + (3 if out_u8 is not None else 0))):
+            check(lib().sc_image_prep_u8(dp + head, plan.packed_bytes, hp, dp, hp + n_off, dp + n_off, hp + n_off + n_geom if has_tab else None,
+                                         dp + n_off + n_geom if has_tab else None, n_tab // 4, B, n, ctypes.cast(m, ctypes.c_void_p), ctypes.cast(sd, ctypes.c_void_p),
+                                         ptr(workspace), workspace.numel(), ptr(out), ptr(out_u8), stream()), "sc_image_prep_u8")
+    return (out, out_u8) if return_u8 else out
+
+
 # ---- fine-tuning HuBERT layers (train_hubert.hip) ----
 def transpose_bf16(src, ld_in, stride_in, rows, cols, batch, rows_padded=None, out=None, ld_out=None, stride_out=None):
     """batch of [rows, cols] bf16 matrices (row r of matrix z at src + z*stride_in + r*ld_in) -> out bf16 [batch, cols, rows_padded] (zero padded);
