@@ -235,6 +235,39 @@ int sc_posconv_finish(const void* x, const int32_t* valid, const void* conv, con
 /* sc_crop_pad: out[b,j] = j < lens[b] ? wav[b, starts[b]+j] : 0 -- train-mode random crop (audio_transforms.py:5-23; offsets drawn on the
  * host exactly as the reference draws them) + zero right-padding (speech_encoder_plus.py:510-518) for the whole batch in one launch. */
 int sc_crop_pad(const float* wav, int64_t ld, const int32_t* starts, const int32_t* lens, float* out, int B, int Lout, void* stream);
+/* sc_wave_prep: the audio side of the data hand-over for a ragged batch of raw PCM utterances in ONE call: int16 -> f32, mono mix, rational-ratio resampling
+ *   to the model's rate, the train-mode crop window and zero right-padding to [B, Lout] (what `librosa.load(path, sr=16000)` in avssl/data/base_dataset.py:70-87
+ *   and random_crop_max_length + re-padding in speech_encoder_plus.py:510-518 do per utterance on the host).  ARITHMETIC CONTRACT (restated in
+ *   speechclip_amd/data/audio_transforms.py, whose float64 execution the tests judge against):
+ *     mono f32 sample  int16: x = (float)(sum_c s_c) * (1.0f / (C * 32768)): every step exact in f32 for C in {1, 2}, so at a matching rate the output equals
+ *                      np.mean(pcm.astype(np.float32) / 32768, axis=1) bit for bit.  f32: x = s (C = 1), (s_0 + s_1) * 0.5f (C = 2).
+ *     ratio            L / M = dst / src reduced by their gcd; n_out = (frames * L + M - 1) / M in 64-bit integers.  L == M == 1 (table = -1, K = 0):
+ *                      y[n] = x[n], no table is read.
+ *     resampler        polyphase Kaiser-windowed sinc (the project's own design; no parity with soxr / librosa is claimed).  In the up-sampled domain
+ *                      fc = ROLLOFF * 0.5 / max(L, M), W = Z / (2 fc), h(t) = L * 2 fc * sinc(2 fc t) * I0(beta * sqrt(1 - (t / W)^2)) / I0(beta) for
+ *                      |t| <= W and 0 outside; Z = 16, beta = 8.56, ROLLOFF = 0.85 = 17 / 20, so `|t| <= W` is the integer test 17 |t| <= 320 max(L, M).
+ *                      Output n: u = n * M (int64), j0 = u div L, p = u mod L; y[n] = sum_k taps[p][k] * x[j_k] over the inputs j_k with
+ *                      |p + (j0 - j_k) * L| <= W in ascending j, x = 0 outside [0, frames); fp32 accumulation in that order inside one thread.
+ *                      taps[p][k] = h evaluated in double on the host and rounded once to f32; K = the largest tap count of any phase (rows are zero
+ *                      beyond their own count; the kernel stops at the count).
+ *   packed   device bytes [packed_bytes]: the utterances back to back (any gaps allowed), each frame-interleaved, frames x C samples
+ *   offsets  int64 [B]: byte offset of utterance b in `packed`, a multiple of its frame size (C * 2 or C * 4 bytes)
+ *   geom     int64 [B][SC_WAVE_PREP_GEOM]: frames, C (1 | 2), fmt (SC_WAVE_PREP_I16 | SC_WAVE_PREP_F32), L, M, K, table (f32 index of the utterance's [L][K]
+ *            tap table in `tables`; -1 = identity rate), start, len (the crop window in OUTPUT samples)
+ *   tables   f32 [tables_len]: one [L][K] table per distinct rate; may be NULL when no utterance resamples.  L * K <= SC_WAVE_PREP_MAX_TABLE.
+ *   offsets / geom / tables are passed TWICE, as host memory (`*_host`: every rule is checked there before any launch) and as the device copy of the same
+ *   bytes the kernel reads.  out f32: out[b * ld + j] = y_b[start_b + j] for j < len_b and exactly 0.0f for len_b <= j < Lout (ld >= Lout).
+ *   Only the crop window is computed.  Every output element is written once; one launch; no atomics, no host synchronisation, 64-bit addressing.
+ *   Refused (nonzero rc + sc_last_error, nothing launched): C outside {1, 2}; unknown fmt; frames < 0; L, M <= 0 or not coprime; a window outside [0, n_out];
+ *   len > Lout; an utterance outside `packed` (or a misaligned offset); a table index or extent outside `tables`; K that is not the support's tap count (or a
+ *   table given at identity rate); NULL tables when an utterance resamples; a table over the cap; a decimation so steep (about M / L > 30) that one block's
+ *   input span does not fit its staging buffer; ld < Lout. */
+#define SC_WAVE_PREP_GEOM 9
+#define SC_WAVE_PREP_I16 0
+#define SC_WAVE_PREP_F32 1
+#define SC_WAVE_PREP_MAX_TABLE 65536
+int sc_wave_prep(const void* packed, int64_t packed_bytes, const int64_t* offsets_host, const int64_t* offsets, const int64_t* geom_host, const int64_t* geom,
+                 const float* tables_host, const float* tables, int64_t tables_len, int B, float* out, int64_t ld, int64_t Lout, void* stream);
 
 /* ---- CLIP ViT stem -- openai VisionTransformer.forward up to ln_pre (clip_official.py:209) ----- */
 /* sc_image_normalize_u8: torchvision ToTensor + Normalize of CLIP's `_transform` (openai clip.py `_transform`, called through

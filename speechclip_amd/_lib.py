@@ -99,6 +99,7 @@ def _declare(L):
         "sc_posconv_pack": ([P, P, P, I, I, I, I, I, P], c_int),
         "sc_posconv_finish": ([P, P, P, P, P, P, P, I, I, I, I, I, F, P], c_int),
         "sc_crop_pad": ([P, L64, P, P, P, I, I, P], c_int),
+        "sc_wave_prep": ([P, L64, P, P, P, P, P, P, L64, I, P, L64, L64, P], c_int),
         "sc_conv0_fwd_packed": ([P, L64, L64, P, P, P, P, I, I, I, P, I, I, I, P, P], c_int),
         "sc_posconv_conv_packed": ([P, P, P, P, P, I, I, I, I, I, P], c_int),
         "sc_posconv_finish_packed": ([P, P, P, P, P, P, P, P, I, L64, I, I, I, F, P], c_int),

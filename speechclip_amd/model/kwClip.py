@@ -271,6 +271,12 @@ class KWClipBase(BaseLightningModel):
         return r_ab, r_ba, r_mean
 
     def processWavs(self, wav):
+        """-> (wav, 16 kHz lengths).  Beyond the reference, a list element may be raw host audio: an int16 / float32 array or CPU tensor [n] or [n, C]
+        (16 kHz), a (samples, rate) pair, or the path of a 16-bit PCM .wav file, which is decoded here (data.audio_transforms.load_wav_pcm); the encoder
+        hands such a list to the device in one packed copy (ops.wave_prep)."""
+        if isinstance(wav, (list, tuple)):
+            from ..data.audio_transforms import resolve_wave_list
+            return resolve_wave_list(wav)
         wav_len = [len(x) for x in wav]
         return wav, wav_len
 
@@ -582,6 +588,13 @@ class KWClip_GeneralTransformer(KWClipBase):
         audio_feat, audio_len = self.forward_audio(wav, wav_len)
         c_feat, p_feat, vq, kw = self._branches(audio_feat, audio_len)
         return {"cascaded_audio_feat": c_feat, "parallel_audio_feat": p_feat, "vq_results": vq, "keywords": kw}
+
+    def get_attention_weights(self, wav):
+        """kwClip.py:1480-1496: the cascaded branch's attention maps for visualisation; every element form of processWavs."""
+        wav, wav_len = self.processWavs(wav)
+        self.clip.update_device(self.device)
+        audio_feat, audio_len = self.forward_audio(wav, wav_len)
+        return self.cascaded_branch.getAttentionMap(audio_feat, audio_len)
 
     def feature_extractor_s3prl(self, wav):
         """kwClip.py:1213-1247: encoder hidden states followed by the branches' (cascaded first, then parallel; the branch input itself,

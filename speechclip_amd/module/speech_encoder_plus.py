@@ -17,6 +17,7 @@ import torch
 import torch.nn as nn
 
 from .. import ops
+from ..data.audio_transforms import random_crop_max_length, resolve_wave_list, wave_list_kind  # noqa: F401  (random_crop_max_length lives where the reference keeps it)
 from .hubert import HubertConfig, HubertModel
 from .weighted_sum import WeightedSumLayer
 
@@ -24,13 +25,11 @@ logger = logging.getLogger(__name__)
 FEAT_SELECT_IDX_WEIGHTED_SUM_MODE = "weighted_sum"
 
 
-def random_crop_max_length(audio: torch.Tensor, max_len: int, orig_len: int = 1000000000) -> torch.Tensor:
-    """avssl/data/audio_transforms.py:5-23 (train-mode crop applied inside the encoder forward)."""
-    n = min(len(audio), orig_len)
-    if max_len < 0 or n <= max_len:
-        return audio[:n]
-    start = np.random.randint(n - max_len)
-    return audio[start:start + max_len]
+# What SC_WAVE_PREP=auto does with a list of 1-D float32 host tensors at 16 kHz (the form the per-utterance loop has always served): True = the packed
+# hand-over (sc_wave_prep).  tools/wave_prep_bench.py measured the device entry faster than the loop in 3 of 3 interleaved passes (256 utterances of 2 .. 10 s:
+# 6.93 ms against 9.26 ms per call; profiles/wave_prep_bench.txt).  The two paths give equal bits; SC_WAVE_PREP=host / device decide regardless.  The element
+# forms only the entry serves (int16, stereo, other rates, paths) always take it.
+_WAVE_PREP_AUTO_DEVICE = True
 
 
 def _find_local_ckpt(url: str):
@@ -170,6 +169,51 @@ class FairseqSpeechEncoder_Hubert(nn.Module):
                 return [wav]
         return list(wav)
 
+    @staticmethod
+    def _wave_prep_on_device(wavs: list, dev: torch.device) -> bool:
+        """Which hand-over a list of utterances takes.  SC_WAVE_PREP (read at every call): `host` = the per-utterance loop (16 kHz float tensors only: it
+        cannot serve the other element forms and says so), `device` = sc_wave_prep for every list of host data, `auto` (the default) = sc_wave_prep for the
+        forms only it serves, and for 16 kHz float lists what the measurement decided (_WAVE_PREP_AUTO_DEVICE).  A list that holds a device tensor keeps
+        the loop; the entry has no CPU fallback."""
+        mode = os.environ.get("SC_WAVE_PREP", "auto")
+        if mode not in ("host", "device", "auto"):
+            raise ValueError(f"SC_WAVE_PREP={mode!r}: expected host, device or auto")
+        kind = wave_list_kind(wavs)
+        if kind == "new":
+            if mode == "host":
+                raise ValueError("SC_WAVE_PREP=host keeps the per-utterance loop, which takes 1-D float tensors at 16 kHz only: int16 / stereo / "
+                                 "(samples, rate) / path elements need SC_WAVE_PREP=auto or device")
+            if dev.type != "cuda":
+                from .._lib import SpeechClipHipError
+                raise SpeechClipHipError("int16 / stereo / (samples, rate) / path elements of a wav list are converted by sc_wave_prep on the GPU: "
+                                         "no CPU fallback (move the model to a GPU, or pass 1-D float tensors at 16 kHz)")
+            return True
+        return kind == "float16k" and dev.type == "cuda" and (mode == "device" or (mode == "auto" and _WAVE_PREP_AUTO_DEVICE))
+
+    def _list_to_padded(self, wavs: list, dev: torch.device):
+        """A list of utterances -> (zero right-padded f32 [B, Lmax] on `dev`, 16 kHz lengths); train mode crops to max_audio_len at a random offset."""
+        if self._wave_prep_on_device(wavs, dev):
+            # the packed hand-over (ops.wave_prep, DESIGN 3.9): raw samples cross PCIe once; conversion, mono mix, resampling to 16 kHz, crop and padding
+            # in one library call.  The crop offsets are drawn exactly as random_crop_max_length draws them: one np.random.randint per utterance longer
+            # than max_audio_len (its 16 kHz length), in batch order, before the layer-drop draws of forward.
+            wavs, full = resolve_wave_list(wavs)
+            starts, lens = [], []
+            for n in full:
+                if not self.training or self.max_audio_len < 0 or n <= self.max_audio_len:
+                    starts.append(0); lens.append(n)
+                else:
+                    starts.append(int(np.random.randint(n - self.max_audio_len))); lens.append(self.max_audio_len)
+            with torch.cuda.device(dev):
+                padded = ops.wave_prep(wavs, starts, lens, max(lens))
+        else:
+            if self.training:
+                wavs = [random_crop_max_length(w, self.max_audio_len, len(w)) for w in wavs]
+            lens = [len(w) for w in wavs]
+            padded = torch.zeros(len(wavs), max(lens), device=dev, dtype=torch.float32)
+            for i, w in enumerate(wavs):
+                padded[i, : lens[i]] = w.to(dev, torch.float32)
+        return padded, lens
+
     def forward(self, wav: Union[torch.Tensor, list], wav_len: Union[torch.Tensor, list] = [],
                 feat_select_idx: Union[str, list] = None, return_hidden_states: bool = False) -> Tuple:
         dev = next(self.encoder.parameters()).device
@@ -195,13 +239,7 @@ class FairseqSpeechEncoder_Hubert(nn.Module):
                     starts.append(int(np.random.randint(n - self.max_audio_len))); lens.append(self.max_audio_len)
             padded = ops.crop_pad(wav.to(dev, torch.float32), starts, lens, max(lens))
         else:
-            wavs = self._to_list(wav, wav_len)
-            if self.training:
-                wavs = [random_crop_max_length(w, self.max_audio_len, len(w)) for w in wavs]
-            lens = [len(w) for w in wavs]
-            padded = torch.zeros(len(wavs), max(lens), device=dev, dtype=torch.float32)
-            for i, w in enumerate(wavs):
-                padded[i, : lens[i]] = w.to(dev, torch.float32)
+            padded, lens = self._list_to_padded(self._to_list(wav, wav_len), dev)
         # speech_encoder_plus.py:572-592: `normalize_type` method1 / method2 overwrite every hidden state before they are mixed / returned ("s3prl" instead
         # normalises inside WeightedSumLayer).  They need the reference's padded [B, T] layout (method2 averages over ALL T frames of the padded batch).
         norm_method = self.normalize_type if (self.normalize_hiddenstates and self.normalize_type.startswith("method")) else None

@@ -637,6 +637,66 @@ def crop_pad(wav, starts, lens, Lout):
     return out
 
 
+def wave_prep(clips, starts=None, lens=None, Lout=None):
+    """The audio hand-over on the current device (sc_wave_prep): a list of host utterances -- int16 / float32 arrays or CPU tensors [n] or [n, C] (16 kHz),
+    (samples, rate) pairs, paths of 16-bit PCM .wav files -- -> f32 [B, Lout] at 16 kHz: sample conversion, mono mix, polyphase resampling, the crop window
+    [starts[b], starts[b] + lens[b]) in 16 kHz samples (default: everything) and zero right-padding (Lout defaults to the longest window).  The geometry, the
+    tap tables (cached per rate) and the raw samples go into ONE pinned buffer, cross PCIe in one non-blocking copy, and one library call on the current stream
+    does the rest.  data/audio_transforms.py states the arithmetic."""
+    return _wave_prep(clips, starts, lens, Lout)
+
+
+def _wave_prep(clips, starts=None, lens=None, Lout=None, device=None, out=None, pad_bytes=0):
+    """wave_prep with the knobs the tests need: device (any spelling of a GPU, default the current one), out = a caller-owned f32 [B, >= Lout] view with unit
+    column stride to write into (the tests put it between sentinel guards, rows apart), pad_bytes: gaps around every utterance, filled with a pattern that
+    reads as NaN in f32 and 0x7fff in int16."""
+    import numpy as np
+    from .data.audio_transforms import plan_wave_batch
+    if not torch.cuda.is_available():
+        raise _lib.SpeechClipHipError("speechclip_amd ops need a GPU: wave_prep has no CPU fallback (int16 / stereo / other-rate / path elements of a wav list "
+                                      "are served by the device entry only)")
+    dev = torch.device("cuda") if device is None else torch.device(device)
+    if dev.type != "cuda":
+        raise _lib.SpeechClipHipError("speechclip_amd ops need device tensors (no CPU fallback)")
+    if dev.index is None:
+        dev = torch.device("cuda", torch.cuda.current_device())
+    plan = plan_wave_batch(clips, starts, lens, pad_bytes=pad_bytes)
+    B = len(plan.clips)
+    longest = int(plan.geom[:, 8].max()) if B else 0
+    Lout = longest if Lout is None else int(Lout)
+    if Lout < longest:
+        raise ValueError(f"wave_prep: Lout={Lout} is shorter than the longest window ({longest})")
+    # one pinned buffer: offsets | geom | tables | (16-byte aligned) samples; a fresh pinned tensor per call (see image_prep)
+    n_off, n_geom, n_tab = plan.offsets.nbytes, plan.geom.nbytes, plan.tables.nbytes
+    head = (n_off + n_geom + n_tab + 15) // 16 * 16
+    host = torch.empty(max(head + plan.packed_bytes, 16), dtype=torch.uint8, pin_memory=True)
+    hb = host.numpy()
+    hb[:n_off] = plan.offsets.view(np.uint8)
+    hb[n_off:n_off + n_geom] = plan.geom.reshape(-1).view(np.uint8)
+    hb[n_off + n_geom:n_off + n_geom + n_tab] = plan.tables.view(np.uint8)
+    if pad_bytes:
+        hb[head:head + plan.packed_bytes].view(np.uint16)[:] = 0x7fff
+    for b, (x, _) in enumerate(plan.clips):
+        o = head + int(plan.offsets[b])
+        hb[o:o + x.nbytes] = x.reshape(-1).view(np.uint8)
+    with torch.cuda.device(dev):
+        d = host.to(dev, non_blocking=True)
+        if out is None:
+            out = torch.empty(B, Lout, device=dev, dtype=torch.float32)
+        if not (out.is_cuda and out.device == dev and out.dtype == torch.float32 and out.dim() == 2 and out.shape[0] == B and out.shape[1] >= Lout
+                and (out.stride(1) == 1 or out.shape[1] <= 1) and (B <= 1 or out.stride(0) >= Lout)):
+            raise ValueError(f"wave_prep: output buffer must be an f32 [{B}, >= {Lout}] tensor on {dev} with unit column stride")
+        if B == 0 or Lout == 0:
+            return out[:, :Lout]
+        hp, dp = host.data_ptr(), d.data_ptr()
+        has_tab = n_tab > 0
+        with _HbmSpan("wave_prep", plan.packed_bytes + B * Lout * 4):
+            check(lib().sc_wave_prep(dp + head, plan.packed_bytes, hp, dp, hp + n_off, dp + n_off, hp + n_off + n_geom if has_tab else None,
+                                     dp + n_off + n_geom if has_tab else None, n_tab // 4, B, ptr(out), out.stride(0) if B > 1 else max(out.stride(0), Lout), Lout,
+                                     stream()), "sc_wave_prep")
+    return out[:, :Lout]
+
+
 def vit_patchify(img, p, Kpad):
     _need_cuda(img)
     B, C, R, _ = img.shape
