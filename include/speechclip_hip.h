@@ -523,6 +523,13 @@ int sc_attn_softmax_bwd_heads(const float* S, const float* dP, int64_t ld, int64
  * rows (row b*L + t of stride ld_qkv, head h at column h*64), dO and O (stride ld_o); the fp32 S / dP images are never written. */
 int sc_attn_bwd_probs(const void* q, const void* k, const void* v, int64_t ld_qkv, const void* dO, const void* O, int64_t ld_o, const int32_t* klens,
                       void* P, void* dS, int B, int H, int L, int Lp, float scale, float drop_p, uint32_t seed, void* stream);
+/* Argument rules (a violation returns non-zero with the message in sc_last_error(); a call of size zero -- n, rows or cols <= 0 -- returns 0 and
+ * touches nothing; every operand is aligned to its element size):
+ *   sc_gelu_bwd_bf16       n even; u, dh, du 16-byte aligned.
+ *   sc_layernorm_bwd_bf16  D a multiple of 64, at most 1024; no operand null; x, dy, dx 8-byte aligned when D % 256 == 0 (the 8-byte kernel; rows are
+ *                          contiguous, so the base decides for every row); part holds sc_layernorm_bwd_bf16_partials(rows) rows of 2 D floats.
+ *   sc_colsum_bf16         no operand null; cols <= 65535 * 256; ld >= cols; ws holds sc_colsum_bf16_workspace_bytes(rows, cols) bytes.
+ *   sc_axpy_bf16           n even; y, x not null and 4-byte aligned (the kernel moves pairs). */
 int sc_gelu_bwd_bf16(const void* u, const void* dh, void* du, int64_t n, void* stream);
 int64_t sc_layernorm_bwd_bf16_partials(int64_t rows);
 int sc_layernorm_bwd_bf16(const void* x, const void* dy, const float* gamma, void* dx, float* part, int64_t rows, int D, float eps, void* stream);

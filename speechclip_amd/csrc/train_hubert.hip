@@ -498,6 +498,11 @@ extern "C" int64_t sc_layernorm_bwd_bf16_partials(int64_t rows) {   // number of
 extern "C" int sc_layernorm_bwd_bf16(const void* x, const void* dy, const float* gamma, void* dx, float* part, int64_t rows, int D, float eps, void* stream) {
     SC_CHECK_ARG(D > 0 && D <= 1024 && D % 64 == 0, "sc_layernorm_bwd_bf16: D=%d must be a multiple of 64, <= 1024", D);
     if (rows <= 0) return 0;
+    SC_CHECK_ARG(x && dy && gamma && dx && part, "sc_layernorm_bwd_bf16: null operand");
+    SC_CHECK_ARG(D % 256 != 0 || (((uintptr_t)x | (uintptr_t)dy | (uintptr_t)dx) & 7) == 0,
+                 "sc_layernorm_bwd_bf16: D=%d runs the 8-byte kernel: x, dy and dx must be 8-byte aligned", D);
+    SC_CHECK_ARG((((uintptr_t)x | (uintptr_t)dy | (uintptr_t)dx) & 1) == 0 && (((uintptr_t)gamma | (uintptr_t)part) & 3) == 0,
+                 "sc_layernorm_bwd_bf16: operands must be aligned to their element size");
     const int rpb = rows >= 4096 ? 32 : 4;
     if (D % 256 == 0)
         hipLaunchKernelGGL(ln_bwd_bf16_vec_kernel, dim3((unsigned)((rows + rpb - 1) / rpb)), dim3(256), 0, (hipStream_t)stream, (const bf16_t*)x,
@@ -516,6 +521,10 @@ extern "C" int64_t sc_colsum_bf16_workspace_bytes(int64_t rows, int cols) {
 
 extern "C" int sc_colsum_bf16(const void* x, int64_t ld, int64_t rows, int cols, float* ws, float* out, int accumulate, void* stream) {
     if (rows <= 0 || cols <= 0) return 0;
+    SC_CHECK_ARG(x && ws && out, "sc_colsum_bf16: null operand");
+    SC_CHECK_ARG(cols <= 65535 * 256, "sc_colsum_bf16: cols=%d must be at most 65535 * 256", cols);
+    SC_CHECK_ARG(ld >= cols, "sc_colsum_bf16: ld=%lld must be at least cols=%d", (long long)ld, cols);
+    SC_CHECK_ARG(((uintptr_t)x & 1) == 0 && (((uintptr_t)ws | (uintptr_t)out) & 3) == 0, "sc_colsum_bf16: operands must be aligned to their element size");
     const int rpb = rows >= 65536 ? 128 : 64;
     const int nparts = (int)((rows + rpb - 1) / rpb);
     hipLaunchKernelGGL(colsum_bf16_stage1_kernel, dim3(nparts, (cols + 255) / 256), dim3(256), 0, (hipStream_t)stream, (const bf16_t*)x, ld, rows, cols, ws, rpb);
@@ -527,6 +536,8 @@ extern "C" int sc_colsum_bf16(const void* x, int64_t ld, int64_t rows, int cols,
 extern "C" int sc_axpy_bf16(void* y, const void* x, float alpha, int64_t n, void* stream) {
     SC_CHECK_ARG(n % 2 == 0, "sc_axpy_bf16: n=%lld must be even", (long long)n);
     if (n <= 0) return 0;
+    SC_CHECK_ARG(y && x, "sc_axpy_bf16: null operand");
+    SC_CHECK_ARG((((uintptr_t)y | (uintptr_t)x) & 3) == 0, "sc_axpy_bf16: y and x must be 4-byte aligned (the kernel moves pairs)");
     hipLaunchKernelGGL(axpy_bf16_kernel, dim3((unsigned)((n / 2 + 255) / 256)), dim3(256), 0, (hipStream_t)stream, (bf16_t*)y, (const bf16_t*)x, alpha, n);
     SC_CHECK_LAUNCH();
     return 0;
