@@ -665,6 +665,36 @@ int sc_attention_hd_bwd(const void* q, const void* k, const void* v, const void*
                         int64_t q_bs, int64_t q_rs, int64_t kv_bs, int64_t kv_rs, int64_t o_bs, int64_t o_rs,
                         void* dq, int64_t dq_bs, int64_t dq_rs, void* dk, void* dv, int64_t dkv_bs, int64_t dkv_rs,
                         float scale, float drop_p, uint32_t seed, void* workspace, void* stream);
+
+/* ---- Gallery search: the K nearest gallery rows of every query row, fused fp32 similarity + top-K (csrc/search.hip).  No [Q, N] score image is formed:
+ * the scores of a (query tile, gallery tile) pair live in MFMA accumulators, are filtered against the row's current K-th entry and only survivors reach a
+ * per-row candidate list in LDS.  ARITHMETIC CONTRACT (restated on the host in tests/search_ref.py, which the tests judge against):
+ *   score     s(i, j) = the fp32 chain  acc = +0.0f;  for e = 0 .. E-1 ascending:  acc = fmaf(q[i*ld_q + e], g[j*ld_g + e], acc)  -- one rounding per step, one
+ *             accumulator per (i, j), never split over E and never reordered.  It is formed on v_mfma_f32_32x32x2_f32, whose result is that chain (k = 2t from
+ *             lanes 0..31, k = 2t + 1 from lanes 32..63, in that order); subnormals are kept.
+ *   order     pairs (s(i, j), j) are ordered by score descending, then j ascending (sc_topk_rows_f32's tie rule).  A NaN score takes no part.
+ *   result    for query i the first K pairs of that order over j in [0, N): vals f32 [Q, K] = the scores, idx i64 [Q, K] = idx_base + j.  With fewer than K
+ *             comparable scores the remaining slots hold -inf / -1.
+ *   pure      the bits of row i of vals / idx depend on q[i, :E], g[:N, :E], K and idx_base only: not on the other queries, on i's position in the call, on
+ *             n_split, on the previous contents of `workspace`, and on K only as a prefix (the result for K' < K is the first K' columns of the result for K).
+ *             No global atomics; LDS counters only hand out candidate slots, and the list is always rebuilt by rank in the total order above.
+ *   splits    the gallery is cut into n_split ranges of ceil(N / n_split) rows (trailing ranges may be empty), one block per (query tile, range), so that a
+ *             single query against 10^6 rows still fills the chip; each block writes its K-list to `workspace` ([Q][n_split][K] i64, then the same in f32:
+ *             sc_search_workspace_bytes = 12 Q n_split K bytes, 0 for one split, which writes vals / idx directly) and sc_topk_merge joins them.
+ *             n_split = 0: sc_search_splits(Q, N, K) = clamp(min(ceil(512 / query_tiles), N / 256), 1, 1024) with query_tiles = ceil(Q / B) and
+ *             B = 128 query rows per block when K <= 64 and Q > 64, else 64.  Both are pure host functions.
+ *   reads     rows [0, Q) of q and [0, N) of g, E elements of each; nothing else.
+ *   refused   (nonzero rc + sc_last_error, nothing launched) E % 4 != 0 or E outside [4, 1024]; ld_q / ld_g < E or not multiples of 4; q or g not 16-byte
+ *             aligned; K outside [1, 128]; K > N; N >= 2^31; n_split outside [0, 1024]; Q < 0; a null operand; no workspace with more than one split.
+ *             Q == 0 returns 0 and launches nothing.
+ * sc_topk_merge: row r of vals_in f32 [Q, L] / idx_in i64 [Q, L] holds L candidates in any order; vals / idx [Q, K] receive the first K by (value
+ *   descending, idx ascending).  Entries with idx < 0 or a NaN value take no part (they are how a short list is padded); missing slots hold -inf / -1.
+ *   Entries of one row are expected to carry distinct idx (an exact duplicate pair is emitted once).  1 <= K <= 128, K <= L; outputs must not alias inputs. */
+int sc_search_splits(int Q, int64_t N, int K);
+int64_t sc_search_workspace_bytes(int Q, int64_t N, int K, int n_split);
+int sc_search_topk(const float* q, int64_t ld_q, const float* g, int64_t ld_g, int Q, int64_t N, int E, int K, int n_split,
+                   int64_t idx_base, float* vals, int64_t* idx, void* workspace, void* stream);
+int sc_topk_merge(const float* vals_in, const int64_t* idx_in, int Q, int L, int K, float* vals, int64_t* idx, void* stream);
 #ifdef __cplusplus
 }
 #endif

@@ -179,6 +179,10 @@ def _declare(L):
         "sc_colsum_det_workspace_bytes": ([I, I], c_int64),
         "sc_colsum_det": ([P, L64, I, I, P, I, P, L64, P], c_int),
         "sc_cls_pool_bwd_det": ([P, L64, P, P, I, L64, I, I, P, P, P, P, P, P, P, P, P, I, I, I, I, I, I, F, U32, P], c_int),
+        "sc_search_splits": ([I, L64, I], c_int),
+        "sc_search_workspace_bytes": ([I, L64, I, I], c_int64),
+        "sc_search_topk": ([P, L64, P, L64, I, L64, I, I, I, L64, P, P, P, P], c_int),
+        "sc_topk_merge": ([P, P, I, I, I, P, P, P], c_int),
     }
     for name, (args, res) in sigs.items():
         fn = getattr(L, name)   # AttributeError here = header/library mismatch: fail loudly

@@ -27,7 +27,7 @@ _VIT_START = os.environ.get("SC_VIT_START", "")       # "" = the image tower sta
                                                        # "head": behind the whole speech tower, beside the pooling / keyword head (the cascaded head is ~2.5 ms of small kernels)
 _SIDE_STREAMS = {}
 from ..base import OrderedNamespace
-from ..module import ClipModel, FairseqSpeechEncoder_Hubert, MLPLayers, S3prlSpeechEncoderPlus, losses, mutualRetrieval
+from ..module import ClipModel, EmbeddingIndex, FairseqSpeechEncoder_Hubert, MLPLayers, S3prlSpeechEncoderPlus, losses, mutualRetrieval
 from ..module.kw_modules import TransformerModels
 from ..module.speechclip_c_modules import vector_quantizers
 from ..module.speechclip_c_modules.kw_bn import Kw_BatchNorm
@@ -104,6 +104,48 @@ class KWClipBase(BaseLightningModel):
         else:
             raise TypeError(f"Unknown text type {type(sents)}")
         return text
+
+    # ---- gallery search (beyond the reference: its retrieval exists only as recall@K inside validation_epoch_end) -------
+    def _embed(self, images=None, sents=None, wav=None) -> torch.Tensor:
+        """The L2-normalised embedding rows of exactly one modality, through the existing entry points, in eval mode under no_grad."""
+        given = [x is not None for x in (images, sents, wav)]
+        if sum(given) != 1:
+            raise ValueError("give exactly one of images, sents, wav")
+        was_training = self.training
+        self.eval()
+        try:
+            with torch.no_grad():
+                if images is not None:
+                    return self.forward_image(images)
+                if sents is not None:
+                    return self.forward_text(sents)
+                feats = self.encode_speech(wav)
+                return feats["cascaded_audio_feat"] if self.config.retrieval.audio_feat_src == "cascaded" else feats["parallel_audio_feat"]
+        finally:
+            self.train(was_training)
+
+    def build_index(self, images=None, sents=None, wav=None, ids=None, batch_size: int = 256) -> EmbeddingIndex:
+        """An EmbeddingIndex over the items of ONE modality (images: paths / decoded frames / a [n, 3, H, W] tensor; sents: sentences / token ids; wav: whatever
+        encode_speech takes).  Every batch of `batch_size` items is encoded and added as one segment; `ids` (int64 tensor or hashables such as paths)
+        label the items, default: their positions."""
+        items = next(x for x in (images, sents, wav, ()) if x is not None)
+        n = len(items)
+        if ids is not None and len(ids) != n:
+            raise ValueError(f"{len(ids)} ids for {n} items")
+        index = None
+        for at in range(0, n, int(batch_size)):
+            part = items[at:at + batch_size]
+            feat = self._embed(images=part if images is not None else None, sents=part if sents is not None else None, wav=part if wav is not None else None)
+            if index is None:
+                index = EmbeddingIndex(feat.shape[1], device=feat.device)
+            index.add(feat, None if ids is None else ids[at:at + batch_size])
+        if index is None:
+            raise ValueError("give exactly one of images, sents, wav, with at least one item")
+        return index
+
+    def search(self, index: EmbeddingIndex, k: int, images=None, sents=None, wav=None):
+        """The k nearest items of `index` for every query of one modality -> (scores f32 [Q, k], positions i64 [Q, k], ids): EmbeddingIndex.search."""
+        return index.search(self._embed(images=images, sents=sents, wav=wav), k)
 
     def forward(self, batch: dict) -> tuple:
         raise NotImplementedError()

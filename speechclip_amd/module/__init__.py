@@ -10,10 +10,11 @@ from . import weighted_sum as _ws
 ClipModel = _clip.ClipModel
 MaskedContrastiveLoss = losses.MaskedContrastiveLoss
 mutualRetrieval = _ret.mutualRetrieval
+EmbeddingIndex = _ret.EmbeddingIndex
 FairseqSpeechEncoder_Hubert = _enc.FairseqSpeechEncoder_Hubert
 S3prlSpeechEncoderPlus = _enc.S3prlSpeechEncoderPlus
 WeightedSumLayer = _ws.WeightedSumLayer
 MLPLayers = _proj.MLPLayers
 
 __all__ = ["ClipModel", "MaskedContrastiveLoss", "mutualRetrieval", "FairseqSpeechEncoder_Hubert", "S3prlSpeechEncoderPlus", "WeightedSumLayer",
-           "MLPLayers", "losses"]
+           "MLPLayers", "losses", "EmbeddingIndex"]

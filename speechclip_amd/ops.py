@@ -1062,6 +1062,40 @@ def retrieval_ranks(score, own_ids, cand_ids):
     return rank
 
 
+# ---- gallery search (search.hip) ----
+def search_topk(q, g, k, n_split=0, idx_base=0, workspace=None):
+    """q f32 [Q, E], g f32 [N, E] (device, last stride 1) -> (vals f32 [Q, k], idx i64 [Q, k]): for every query the k gallery rows with the largest
+    fp32 fmaf-chain score, ordered by (score descending, row ascending); idx = idx_base + row.  No [Q, N] score image is formed (sc_search_topk).
+    n_split = 0: the library's rule.  `workspace`: a caller's uint8 buffer of at least sc_search_workspace_bytes (tests guard it); default: allocated here."""
+    _need_cuda(q, g)
+    assert q.dtype == torch.float32 and g.dtype == torch.float32 and q.dim() == 2 and g.dim() == 2 and q.stride(1) == 1 and g.stride(1) == 1
+    assert q.shape[1] == g.shape[1], (q.shape, g.shape)
+    Q, E = q.shape
+    N, k = g.shape[0], int(k)
+    vals = torch.empty(Q, k, device=q.device, dtype=torch.float32)
+    idx = torch.empty(Q, k, device=q.device, dtype=torch.int64)
+    nbytes = lib().sc_search_workspace_bytes(Q, N, k, int(n_split))
+    if workspace is None and nbytes > 0:
+        workspace = torch.empty(nbytes, device=q.device, dtype=torch.uint8)
+    assert workspace is None or (workspace.is_cuda and workspace.numel() * workspace.element_size() >= nbytes)
+    check(lib().sc_search_topk(ptr(q), q.stride(0), ptr(g), g.stride(0), Q, N, E, k, int(n_split), int(idx_base), ptr(vals), ptr(idx), ptr(workspace),
+                               stream()), "sc_search_topk")
+    return vals, idx
+
+
+def topk_merge(vals, idx, k):
+    """vals f32 [Q, L], idx i64 [Q, L]: L candidates per row in any order -> the first k by (value descending, idx ascending); entries with idx < 0 or a
+    NaN value take no part, missing slots are -inf / -1 (sc_topk_merge)."""
+    _need_cuda(vals, idx)
+    assert vals.dtype == torch.float32 and idx.dtype == torch.int64 and vals.dim() == 2 and vals.shape == idx.shape
+    vals, idx = vals.contiguous(), idx.contiguous()
+    Q, L = vals.shape
+    out_v = torch.empty(Q, int(k), device=vals.device, dtype=torch.float32)
+    out_i = torch.empty(Q, int(k), device=vals.device, dtype=torch.int64)
+    check(lib().sc_topk_merge(ptr(vals), ptr(idx), Q, L, int(k), ptr(out_v), ptr(out_i), stream()), "sc_topk_merge")
+    return out_v, out_i
+
+
 # ---- cascaded tail, training (train_cascaded.hip) ----
 def attn_small_bwd(qkv16, dout, B, L, H, causal=True):
     """qkv bf16 [B*L, 3*H*64] (saved by the forward), dout f32 [B*L, H*64] -> dqkv f32 [B*L, 3*H*64]."""
