@@ -695,6 +695,31 @@ int64_t sc_search_workspace_bytes(int Q, int64_t N, int K, int n_split);
 int sc_search_topk(const float* q, int64_t ld_q, const float* g, int64_t ld_g, int Q, int64_t N, int E, int K, int n_split,
                    int64_t idx_base, float* vals, int64_t* idx, void* workspace, void* stream);
 int sc_topk_merge(const float* vals_in, const int64_t* idx_in, int Q, int L, int K, float* vals, int64_t* idx, void* stream);
+
+/* ---- Gallery search, bf16 storage: sc_search_topk on rows stored in bf16 (csrc/search_bf16.hip) -- half the gallery bytes, the product on the bf16 MFMA.
+ * q is bf16 [Q, E] with row stride ld_q, g is bf16 [N, E] with row stride ld_g (strides in elements); vals, idx, n_split, idx_base, `workspace`
+ * (sc_search_workspace_bytes), the split rule (sc_search_splits) and the merge (sc_topk_merge) are those of sc_search_topk.  BF16 ARITHMETIC CONTRACT
+ * (restated on the host in tests/search_bf16_ref.py):
+ *   score     s(i, j) = sum over e of q[i*ld_q + e] * g[j*ld_g + e].  Every bf16 product is exact in fp32; the products are accumulated in fp32 by
+ *             v_mfma_f32_32x32x16_bf16: one accumulator per (i, j), starting from +0.0f, E walked in ascending groups of 16, never split over blocks.  The
+ *             order of the 16 additions inside one instruction is the hardware's and is NOT stated; what is stated is the bound
+ *             |s(i, j) - exact sum| <= c * 2^-24 * sum over e of |q[i, e] g[j, e]|,  c = 2 E / (1 - 2 E 2^-24)  (E additions, each counted with twice the
+ *             fp32 unit roundoff so that an adder that truncates is covered; derivation in tests/search_bf16_ref.py).  Sums of integers below 2^24 are
+ *             exact.  Subnormal operands and subnormal products are outside the contract (the matrix pipe may flush them).
+ *   order     pairs (s(i, j), j) are ordered by score descending, then j ascending (sc_topk_rows_f32's tie rule).  A NaN score takes no part.
+ *   result    for query i the first K pairs of that order over j in [0, N): vals f32 [Q, K] = the scores, idx i64 [Q, K] = idx_base + j.  With fewer than K
+ *             comparable scores the remaining slots hold -inf / -1.
+ *   pure      the bits of row i of vals / idx depend on q[i, :E], g[:N, :E], K and idx_base only: not on the other queries, on i's position in the call, on
+ *             n_split, on the previous contents of `workspace`, and on K only as a prefix (the result for K' < K is the first K' columns of the result for K).
+ *             No global atomics; LDS counters only hand out candidate slots, and the list is always rebuilt by rank in the total order above.
+ *   splits    as sc_search_topk: n_split ranges of ceil(N / n_split) rows, one block per (query tile, range), partial K-lists in `workspace`
+ *             (12 Q n_split K bytes, none for one split), joined by sc_topk_merge; n_split = 0: sc_search_splits(Q, N, K).
+ *   reads     rows [0, Q) of q and [0, N) of g, E elements of each; nothing else.
+ *   refused   (nonzero rc + sc_last_error, nothing launched) E % 16 != 0 or E outside [16, 1024] (multiples of 16 only: no zero-filled k-slot ever enters a
+ *             sum); ld_q / ld_g < E or not multiples of 8; q or g not 16-byte aligned; K outside [1, 128]; K > N; N >= 2^31; n_split outside [0, 1024];
+ *             Q < 0; a null operand; no workspace with more than one split.  Q == 0 returns 0 and launches nothing. */
+int sc_search_topk_bf16(const void* q, int64_t ld_q, const void* g, int64_t ld_g, int Q, int64_t N, int E, int K, int n_split,
+                        int64_t idx_base, float* vals, int64_t* idx, void* workspace, void* stream);
 #ifdef __cplusplus
 }
 #endif

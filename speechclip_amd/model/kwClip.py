@@ -124,10 +124,10 @@ class KWClipBase(BaseLightningModel):
         finally:
             self.train(was_training)
 
-    def build_index(self, images=None, sents=None, wav=None, ids=None, batch_size: int = 256) -> EmbeddingIndex:
+    def build_index(self, images=None, sents=None, wav=None, ids=None, batch_size: int = 256, storage: str = "fp32") -> EmbeddingIndex:
         """An EmbeddingIndex over the items of ONE modality (images: paths / decoded frames / a [n, 3, H, W] tensor; sents: sentences / token ids; wav: whatever
         encode_speech takes).  Every batch of `batch_size` items is encoded and added as one segment; `ids` (int64 tensor or hashables such as paths)
-        label the items, default: their positions."""
+        label the items, default: their positions.  storage: "fp32" or "bf16" rows (EmbeddingIndex)."""
         items = next(x for x in (images, sents, wav, ()) if x is not None)
         n = len(items)
         if ids is not None and len(ids) != n:
@@ -137,7 +137,7 @@ class KWClipBase(BaseLightningModel):
             part = items[at:at + batch_size]
             feat = self._embed(images=part if images is not None else None, sents=part if sents is not None else None, wav=part if wav is not None else None)
             if index is None:
-                index = EmbeddingIndex(feat.shape[1], device=feat.device)
+                index = EmbeddingIndex(feat.shape[1], device=feat.device, storage=storage)
             index.add(feat, None if ids is None else ids[at:at + batch_size])
         if index is None:
             raise ValueError("give exactly one of images, sents, wav, with at least one item")

@@ -44,10 +44,20 @@ class EmbeddingIndex:
     similarity + top-k, no [Q, N] score image).  Rows are kept as fp32 SEGMENTS, one per `add`; adding never reallocates earlier segments.  A search runs
     every segment with its starting position as idx_base and joins the partial lists with sc_topk_merge; because the score is a fixed fmaf chain per
     (query, row) and ties go to the lower position, the result equals, bit for bit, a search of ONE segment holding the concatenation.
+    storage="bf16" (dim % 16 == 0) keeps the rows in bf16 instead: rows and queries are normalised in fp32 as before and then rounded to bf16 (round to
+    nearest even), and sc_search_topk_bf16 forms the scores -- exact bf16 products summed in fp32, returned as fp32; half the bytes per row, the same
+    segments, positions, ids and merge, and the same one-segment equality.  The default stays fp32.
     There is no host implementation: without the library's GPU `add` / `search` raise SpeechClipHipError, like mutualRetrieval."""
 
-    def __init__(self, dim: int, device=None, normalize: bool = True):
-        self.dim, self.normalize = int(dim), bool(normalize)
+    STORAGES = {"fp32": torch.float32, "bf16": torch.bfloat16}
+    STORAGE_BITS = {"fp32": 32, "bf16": 16}            # how state_dict names the storage
+
+    def __init__(self, dim: int, device=None, normalize: bool = True, storage: str = "fp32"):
+        if storage not in self.STORAGES:
+            raise ValueError(f"storage={storage!r} must be one of {sorted(self.STORAGES)}")
+        if storage == "bf16" and int(dim) % 16 != 0:
+            raise ValueError(f"storage='bf16' needs dim % 16 == 0 (sc_search_topk_bf16), got dim={dim}")
+        self.dim, self.normalize, self.storage = int(dim), bool(normalize), storage
         self.device = torch.device(device) if device is not None else None
         self.segments: List[torch.Tensor] = []
         self.ids: Optional[list] = None            # None: the ids are the running positions
@@ -73,7 +83,8 @@ class EmbeddingIndex:
         if feats.dim() != 2 or feats.shape[1] != self.dim or not feats.is_floating_point():
             raise ValueError(f"expected float rows [n, {self.dim}], got {tuple(feats.shape)} {feats.dtype}")
         rows = feats.detach().to(self._device(feats), torch.float32).contiguous()
-        return ops.l2norm(rows) if self.normalize and rows.shape[0] else rows
+        rows = ops.l2norm(rows) if self.normalize and rows.shape[0] else rows
+        return rows.to(self.STORAGES[self.storage])          # bf16 storage: rounded to nearest even AFTER the fp32 normalisation
 
     def add(self, feats: torch.Tensor, ids: Union[None, torch.Tensor, Sequence[Hashable]] = None) -> "EmbeddingIndex":
         rows = self._rows(feats)
@@ -99,10 +110,11 @@ class EmbeddingIndex:
         if not 1 <= k <= min(128, max(self._n, 1)) or self._n == 0:
             raise ValueError(f"k={k} must be in [1, min(128, {self._n} stored rows)]")
         q = self._rows(queries)
+        search_topk = ops.search_topk_bf16 if self.storage == "bf16" else ops.search_topk
         parts_v, parts_i, base = [], [], 0
         for seg in self.segments:
             kk = min(k, seg.shape[0])
-            v, i = ops.search_topk(q, seg, kk, idx_base=base)
+            v, i = search_topk(q, seg, kk, idx_base=base)
             if kk < k:                             # a segment shorter than k: its list is padded with entries that take no part in the merge
                 v = torch.cat([v, torch.full((q.shape[0], k - kk), float("-inf"), device=dev)], 1)
                 i = torch.cat([i, torch.full((q.shape[0], k - kk), -1, device=dev, dtype=torch.int64)], 1)
@@ -116,19 +128,35 @@ class EmbeddingIndex:
         ids = host if self.ids is None else [[self.ids[p] if p >= 0 else None for p in row] for row in host]
         return scores, pos, ids
 
+    def astype(self, storage: str) -> "EmbeddingIndex":
+        """A new index with the same segment boundaries and ids in the other storage: fp32 -> bf16 rounds the stored rows (to nearest even), bf16 -> fp32
+        widens them exactly."""
+        out = EmbeddingIndex(self.dim, device=self.device, normalize=self.normalize, storage=storage)
+        out.segments = [s.to(self.STORAGES[storage], copy=True) for s in self.segments]
+        out.ids = None if self.ids is None else list(self.ids)
+        out._n = self._n
+        return out
+
     def state_dict(self) -> dict:
-        feats = torch.cat(self.segments, 0).cpu() if self.segments else torch.zeros(0, self.dim)
-        return {"dim": self.dim, "normalize": self.normalize, "feats": feats, "segment_rows": [s.shape[0] for s in self.segments],
+        """Plain host values only (numbers, lists, None, host tensors).  "feats" holds the rows in their storage type (a bf16 tensor for a bf16 index: half
+        the file); "storage" names it by its width in bits, 32 or 16."""
+        feats = torch.cat(self.segments, 0).cpu() if self.segments else torch.zeros(0, self.dim, dtype=self.STORAGES[self.storage])
+        return {"dim": self.dim, "normalize": self.normalize, "storage": self.STORAGE_BITS[self.storage], "feats": feats, "segment_rows": [s.shape[0] for s in self.segments],
                 "ids": None if self.ids is None else list(self.ids)}
 
     @classmethod
     def from_state_dict(cls, sd: dict, device=None) -> "EmbeddingIndex":
-        """Rebuilds the same segments from the stored rows (already normalised when the index normalises: they are not normalised again)."""
-        index = cls(sd["dim"], device=device, normalize=sd["normalize"])
+        """Rebuilds the same segments from the stored rows (already normalised when the index normalises: they are not normalised again).  A dict without
+        a "storage" key was written before bf16 storage existed: fp32."""
+        bits = sd.get("storage", 32)
+        names = {b: name for name, b in cls.STORAGE_BITS.items()}
+        if bits not in names:
+            raise ValueError(f"state dict storage={bits!r} must be one of {sorted(names)} (bits per element)")
+        index = cls(sd["dim"], device=device, normalize=sd["normalize"], storage=names[bits])
         dev = index._device()
         at = 0
         for n in sd["segment_rows"]:
-            index.segments.append(sd["feats"][at:at + n].to(dev, torch.float32).contiguous())
+            index.segments.append(sd["feats"][at:at + n].to(dev, cls.STORAGES[index.storage]).contiguous())
             at += n
         index._n = at
         index.ids = None if sd["ids"] is None else list(sd["ids"])

@@ -1062,13 +1062,11 @@ def retrieval_ranks(score, own_ids, cand_ids):
     return rank
 
 
-# ---- gallery search (search.hip) ----
-def search_topk(q, g, k, n_split=0, idx_base=0, workspace=None):
-    """q f32 [Q, E], g f32 [N, E] (device, last stride 1) -> (vals f32 [Q, k], idx i64 [Q, k]): for every query the k gallery rows with the largest
-    fp32 fmaf-chain score, ordered by (score descending, row ascending); idx = idx_base + row.  No [Q, N] score image is formed (sc_search_topk).
-    n_split = 0: the library's rule.  `workspace`: a caller's uint8 buffer of at least sc_search_workspace_bytes (tests guard it); default: allocated here."""
+# ---- gallery search (search.hip, search_bf16.hip) ----
+def _search_topk(entry, dtype, q, g, k, n_split, idx_base, workspace):
+    """The two storage formats of the fused search: the same shapes, outputs, split rule and workspace; `entry` and the rows' dtype differ."""
     _need_cuda(q, g)
-    assert q.dtype == torch.float32 and g.dtype == torch.float32 and q.dim() == 2 and g.dim() == 2 and q.stride(1) == 1 and g.stride(1) == 1
+    assert q.dtype == dtype and g.dtype == dtype and q.dim() == 2 and g.dim() == 2 and q.stride(1) == 1 and g.stride(1) == 1
     assert q.shape[1] == g.shape[1], (q.shape, g.shape)
     Q, E = q.shape
     N, k = g.shape[0], int(k)
@@ -1078,9 +1076,22 @@ def search_topk(q, g, k, n_split=0, idx_base=0, workspace=None):
     if workspace is None and nbytes > 0:
         workspace = torch.empty(nbytes, device=q.device, dtype=torch.uint8)
     assert workspace is None or (workspace.is_cuda and workspace.numel() * workspace.element_size() >= nbytes)
-    check(lib().sc_search_topk(ptr(q), q.stride(0), ptr(g), g.stride(0), Q, N, E, k, int(n_split), int(idx_base), ptr(vals), ptr(idx), ptr(workspace),
-                               stream()), "sc_search_topk")
+    check(getattr(lib(), entry)(ptr(q), q.stride(0), ptr(g), g.stride(0), Q, N, E, k, int(n_split), int(idx_base), ptr(vals), ptr(idx), ptr(workspace),
+                                stream()), entry)
     return vals, idx
+
+
+def search_topk(q, g, k, n_split=0, idx_base=0, workspace=None):
+    """q f32 [Q, E], g f32 [N, E] (device, last stride 1) -> (vals f32 [Q, k], idx i64 [Q, k]): for every query the k gallery rows with the largest
+    fp32 fmaf-chain score, ordered by (score descending, row ascending); idx = idx_base + row.  No [Q, N] score image is formed (sc_search_topk).
+    n_split = 0: the library's rule.  `workspace`: a caller's uint8 buffer of at least sc_search_workspace_bytes (tests guard it); default: allocated here."""
+    return _search_topk("sc_search_topk", torch.float32, q, g, k, n_split, idx_base, workspace)
+
+
+def search_topk_bf16(q, g, k, n_split=0, idx_base=0, workspace=None):
+    """search_topk on bf16 rows (search_bf16.hip): q bf16 [Q, E], g bf16 [N, E] (device, last stride 1, E % 16 == 0) -> (vals f32 [Q, k], idx i64 [Q, k]).
+    The bf16 products are exact and summed in fp32 on the bf16 MFMA (sc_search_topk_bf16's contract); order, splits and workspace as search_topk."""
+    return _search_topk("sc_search_topk_bf16", bf16, q, g, k, n_split, idx_base, workspace)
 
 
 def topk_merge(vals, idx, k):
