@@ -464,9 +464,7 @@ def posconv(x, valid_i32, wg, bias, gamma, beta, B, Tp, D, G, Kw, out=None, out_
     conv = torch.empty(B * G * Tp * cg, device=x.device, dtype=bf16)
     rc = lib().sc_posconv_conv(ptr(x), ptr(valid_i32), ptr(wg), ptr(conv), B, Tp, D, G, Kw, stream())
     if rc == 1:      # group width not covered by the windowed kernel: pack the sliding windows and use the batched GEMM
-        xg = torch.empty(B * G * (Tp + Kw) * cg + 64, device=x.device, dtype=bf16)
-        check(lib().sc_posconv_pack(ptr(x), ptr(valid_i32), ptr(xg), B, Tp, D, G, Kw, stream()), "sc_posconv_pack")
-        gemm_batched(xg, cg, (Tp + Kw) * cg, wg, cg * Kw * cg, G, conv, cg, Tp * cg, None, Tp, cg, Kw * cg, B * G)
+        _posconv_pack_gemm(x, valid_i32, wg, conv, B, Tp, D, G, Kw)
     else:
         check(rc, "sc_posconv_conv")
     if out is None:
@@ -1504,8 +1502,7 @@ def posconv_conv(x, valid_i32, wg, B, Tp, D, G, Kw):
     conv = torch.empty(B * G * Tp * cg, device=x.device, dtype=bf16)
     rc = lib().sc_posconv_conv(ptr(x), ptr(valid_i32), ptr(wg), ptr(conv), B, Tp, D, G, Kw, stream())
     if rc == 1:
-        xg = posconv_pack(x, valid_i32, B, Tp, D, G, Kw)
-        gemm_batched(xg, cg, (Tp + Kw) * cg, wg, cg * Kw * cg, G, conv, cg, Tp * cg, None, Tp, cg, Kw * cg, B * G)
+        _posconv_pack_gemm(x, valid_i32, wg, conv, B, Tp, D, G, Kw)
     else:
         check(rc, "sc_posconv_conv")
     return conv
@@ -1515,8 +1512,30 @@ def posconv_pack(x, valid_i32, B, Tp, D, G, Kw):
     """Sliding-window layout of the masked input: bf16 [B, G, Tp + Kw, D/G] (+64 slack elements), Kw/2 zero rows in front."""
     cg = D // G
     xg = torch.empty(B * G * (Tp + Kw) * cg + 64, device=x.device, dtype=bf16)
+    xg[B * G * (Tp + Kw) * cg:].zero_()
     check(lib().sc_posconv_pack(ptr(x), ptr(valid_i32), ptr(xg), B, Tp, D, G, Kw, stream()), "sc_posconv_pack")
     return xg
+
+
+def _posconv_pack_gemm(x, valid_i32, wg, conv, B, Tp, D, G, Kw):
+    """The route of the group widths the windowed kernel does not take: pack the sliding windows (sc_posconv_pack), then conv[b][g][t][:] = wg[g] . (the Kw * cg elements of
+    slab (b, g) from row t on), one batched GEMM over overlapping rows.  The GEMM reads 16-byte rows and takes K in multiples of 64, so a group width that is no multiple
+    of 8 (D/G = 68) is widened with zero channels and a window length that is no multiple of 64 with zero weight columns: what a row reads past its window are the next
+    rows' elements (finite, times zero) or the zeroed slack behind xg."""
+    pad = torch.nn.functional.pad
+    cg = D // G
+    cgp = (cg + 7) // 8 * 8
+    w = wg.reshape(G, cg, Kw, cg)
+    if cgp != cg:
+        x = pad(x.reshape(B * Tp, G, cg), (0, cgp - cg)).reshape(B * Tp, G * cgp)
+        w = pad(w, (0, cgp - cg))
+    K = Kw * cgp
+    Kp = (K + 63) // 64 * 64
+    w = w.reshape(G, cg, K)
+    if Kp != K:
+        w = pad(w, (0, Kp - K))
+    xg = posconv_pack(x, valid_i32, B, Tp, G * cgp, G, Kw)
+    gemm_batched(xg, cgp, (Tp + Kw) * cgp, w.contiguous(), cg * Kp, G, conv, cg, Tp * cg, None, Tp, cg, Kp, B * G)
 
 
 # The per-utterance kernels serve both layouts: uniform rows (B utterances of Tp rows each) are the packed layout with row_off[b] = b * Tp.  row_off_i32 (B + 1
