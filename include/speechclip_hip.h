@@ -720,6 +720,45 @@ int sc_topk_merge(const float* vals_in, const int64_t* idx_in, int Q, int L, int
  *             Q < 0; a null operand; no workspace with more than one split.  Q == 0 returns 0 and launches nothing. */
 int sc_search_topk_bf16(const void* q, int64_t ld_q, const void* g, int64_t ld_g, int Q, int64_t N, int E, int K, int n_split,
                         int64_t idx_base, float* vals, int64_t* idx, void* workspace, void* stream);
+
+/* ---- Gallery search by item: the K nearest DISTINCT items of every query row, the query's own item left out (csrc/search_items.hip).  A gallery is rarely
+ * one row per thing (five spoken captions per image): g_item gives every gallery row an item code, and the selection of sc_search_topk /
+ * sc_search_topk_bf16 gets a predicate and a tie rule -- no new score.  sc_search_items takes fp32 rows, sc_search_items_bf16 bf16 rows; scores, strides,
+ * alignment, the rules for E, K in [1, 128], n_split, idx_base and N < 2^31 are exactly those of sc_search_topk and sc_search_topk_bf16 respectively.
+ * SELECTION CONTRACT (restated on the host in tests/search_items_ref.py):
+ *   score      the plain entry's s(i, j) of the same format, bit for bit: fp32 rows the ascending fmaf chain of sc_search_topk, bf16 rows the contract of
+ *              sc_search_topk_bf16 (the same loading, staging and MFMA code is compiled into both).
+ *   eligible   eligible(i, j) means: s(i, j) is not NaN and (q_skip == NULL or q_skip[i] < 0 or g_item[j] != q_skip[i]).  g_item is int32 [N] with codes
+ *              >= 0 and is required (non-null); q_skip is int32 [Q] or NULL.
+ *   order      pairs (s(i, j), j) are ordered by score descending, then j ascending, as before.
+ *   result     distinct == 0: the first K eligible pairs of query i in that order.  distinct != 0: the REPRESENTATIVE of an item code c is the first eligible
+ *              pair, in that order, among the rows with g_item[j] == c; the result is the first K representatives in that order.
+ *   outputs    vals f32 [Q, K] = the scores, idx i64 [Q, K] = idx_base + j, items i32 [Q, K] = g_item[j].  Missing slots hold -inf / -1 / -1.
+ *   prefix     in both modes the result for K' < K is the first K' columns of the result for K.
+ *   identities with distinct == 0 and q_skip == NULL, vals and idx equal the plain entry's bit for bit; the same holds with distinct != 0 when all codes in
+ *              g_item are different.
+ *   pure       as the plain entries: the bits of row i depend on q[i, :E], g[:N, :E], g_item[:N], q_skip[i], distinct, K and idx_base only -- not on the other
+ *              queries, on i's position in the call, on n_split or on the previous contents of `workspace`.  No global atomics; LDS counters only hand out
+ *              candidate slots; the list is rebuilt by rank among the entries that no entry of the same item code precedes.
+ *   splits     the same ranges and auto rule (sc_search_splits).  Each block writes its K-list as (idx i64, vals f32, items i32) to `workspace`
+ *              ([Q][n_split][K] of each, in that order: sc_search_items_workspace_bytes = 16 Q n_split K bytes, 0 for one split, which writes the outputs
+ *              directly) and sc_topk_merge_items joins them.  Joining per-split lists is exact also with `distinct`: an item's representative over the
+ *              whole gallery is its representative inside its split, and if it is missing from that split's K-list, K other items have representatives
+ *              before it there -- and those, or better ones, come before it over the whole gallery, so the item is not among the first K.
+ *   reads      rows [0, Q) of q and [0, N) of g, E elements of each; g_item[0 .. N); q_skip[0 .. Q) if given; nothing else.
+ *   refused    (nonzero rc + sc_last_error naming the value, nothing launched) every refusal of the plain entry of the same format, a null g_item and a null
+ *              items.  Q == 0 returns 0 and launches nothing.
+ * sc_topk_merge_items: row r of vals_in f32 [Q, L] / idx_in i64 [Q, L] / items_in i32 [Q, L] holds L candidates in any order.  Entries with idx < 0 or a
+ *   NaN value take no part.  distinct == 0: sc_topk_merge with the item codes carried along.  distinct != 0: only the first pair of each item code, in (value
+ *   descending, idx ascending) order, survives; then the first K of the survivors; L <= 131072 (one bit per candidate in LDS).  Missing slots hold
+ *   -inf / -1 / -1.  1 <= K <= 128, K <= L; outputs must not alias inputs. */
+int64_t sc_search_items_workspace_bytes(int Q, int64_t N, int K, int n_split);
+int sc_search_items(const float* q, int64_t ld_q, const float* g, int64_t ld_g, int Q, int64_t N, int E, int K, int n_split, int64_t idx_base,
+                    const int32_t* g_item, const int32_t* q_skip, int distinct, float* vals, int64_t* idx, int32_t* items, void* workspace, void* stream);
+int sc_search_items_bf16(const void* q, int64_t ld_q, const void* g, int64_t ld_g, int Q, int64_t N, int E, int K, int n_split, int64_t idx_base,
+                         const int32_t* g_item, const int32_t* q_skip, int distinct, float* vals, int64_t* idx, int32_t* items, void* workspace, void* stream);
+int sc_topk_merge_items(const float* vals_in, const int64_t* idx_in, const int32_t* items_in, int Q, int L, int K, int distinct, float* vals, int64_t* idx,
+                        int32_t* items, void* stream);
 #ifdef __cplusplus
 }
 #endif

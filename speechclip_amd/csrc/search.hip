@@ -3,11 +3,12 @@
 //                      ascending order, one accumulator chain, no split over E), kept in accumulators; every score is filtered against its row's current
 //                      K-th entry, survivors go to a per-row LDS candidate buffer, and a full buffer is folded into the row's sorted top-K list by RANK in
 //                      the total order (score descending, j ascending) -- the buffer may fill in any order, the list cannot tell.  The block body is
-//                      search_core.h's search_block, shared with the bf16-row kernel of search_bf16.hip; F32Rows below is the fp32 loading and product.
+//                      search_core.h's search_block, shared with the bf16-row kernel of search_bf16.hip; F32Rows (search_rows.h) is the fp32 loading and product.
 //   topk_merge_kernel  L candidates per row -> the first K of that order (the partial lists of the splits, of gallery segments, of ranks).
 // No global atomics; the LDS counters only hand out buffer slots.  Every output element is written once.
 #include "common.h"
 #include "search_core.h"
+#include "search_rows.h"
 #include "../../include/speechclip_hip.h"
 
 namespace {
@@ -16,70 +17,6 @@ using namespace search_core;
 
 constexpr int MIN_SPLIT_ROWS = 256;
 constexpr int TARGET_BLOCKS = 512;
-
-// fp32 rows on v_mfma_f32_32x32x2_f32 (search_core.h: what an operand format supplies)
-struct F32Rows {
-    using elem = float;
-    static constexpr int LDT = KC + 4;   // LDS row stride in floats: 68 r mod 64 = 4 r walks all sixteen 4-bank slots over 16 rows: ds_read_b128 is conflict-free
-    struct unit { f32x4_t x0, x1; };
-    // 8 consecutive floats of one row from e (a multiple of 8), only those below E (E % 4 == 0: whole 16-byte halves); an absent row reads nothing
-    static __device__ __forceinline__ void load(const float* __restrict__ row, bool row_ok, int e, int E, unit& u) {
-        const f32x4_t z = {0.f, 0.f, 0.f, 0.f};
-        u.x0 = row_ok && e < E ? *(const f32x4_t*)(row + e) : z;
-        u.x1 = row_ok && e + 4 < E ? *(const f32x4_t*)(row + e + 4) : z;
-    }
-    // The 32x32x2 MFMA takes k = 2t from lanes 0..31 and k = 2t + 1 from lanes 32..63, so a group of 8 is stored even elements first: lane half h then reads
-    // its four k-steps (e = 2t + h, t = 0..3) with one ds_read_b128 at offset 4h.
-    static __device__ __forceinline__ void store(float* dst, const unit& u) {
-        *(f32x4_t*)dst = f32x4_t{u.x0[0], u.x0[2], u.x1[0], u.x1[2]};
-        *(f32x4_t*)(dst + 4) = f32x4_t{u.x0[1], u.x0[3], u.x1[1], u.x1[3]};
-    }
-    // rq / rg: this lane's row of the wave's first query / gallery tile in the stage images; e0: the stage's first element
-    template <int WQ>
-    static __device__ __forceinline__ void stage(f32x16_t (&acc)[WQ][2], const float* rq, const float* rg, int h, int e0, int E) {
-        const float* aq = rq + 4 * h;
-        const float* bg = rg + 4 * h;
-        if (e0 + KC <= E) {                              // a whole stage: straight-line code, the fragment reads run ahead of the MFMAs
-            f32x4_t a4[KC / 8][WQ], b4[KC / 8][2];
-#pragma unroll
-            for (int g8 = 0; g8 < KC / 8; ++g8) {
-#pragma unroll
-                for (int a = 0; a < WQ; ++a) a4[g8][a] = *(const f32x4_t*)(aq + a * 32 * LDT + 8 * g8);
-#pragma unroll
-                for (int b = 0; b < 2; ++b) b4[g8][b] = *(const f32x4_t*)(bg + b * 32 * LDT + 8 * g8);
-            }
-#pragma unroll
-            for (int g8 = 0; g8 < KC / 8; ++g8)
-#pragma unroll
-                for (int t = 0; t < 4; ++t)
-#pragma unroll
-                    for (int a = 0; a < WQ; ++a)
-#pragma unroll
-                        for (int b = 0; b < 2; ++b) acc[a][b] = __builtin_amdgcn_mfma_f32_32x32x2f32(a4[g8][a][t], b4[g8][b][t], acc[a][b], 0, 0, 0);
-        } else {                                         // the last stage of a row: E % 4 == 0, so a group of 8 has 4 k-steps or 2
-#pragma unroll
-            for (int g8 = 0; g8 < KC / 8; ++g8) {
-                if (e0 + 8 * g8 < E) {
-                    f32x4_t a4[WQ], b4[2];
-#pragma unroll
-                    for (int a = 0; a < WQ; ++a) a4[a] = *(const f32x4_t*)(aq + a * 32 * LDT + 8 * g8);
-#pragma unroll
-                    for (int b = 0; b < 2; ++b) b4[b] = *(const f32x4_t*)(bg + b * 32 * LDT + 8 * g8);
-                    const bool whole = e0 + 8 * g8 + 4 < E;
-#pragma unroll
-                    for (int t = 0; t < 4; ++t) {
-                        if (t < 2 || whole) {
-#pragma unroll
-                            for (int a = 0; a < WQ; ++a)
-#pragma unroll
-                                for (int b = 0; b < 2; ++b) acc[a][b] = __builtin_amdgcn_mfma_f32_32x32x2f32(a4[a][t], b4[b][t], acc[a][b], 0, 0, 0);
-                        }
-                    }
-                }
-            }
-        }
-    }
-};
 
 template <int WQ, int KL>
 __global__ __launch_bounds__(256) void search_kernel(const float* __restrict__ q, int64_t ld_q, const float* __restrict__ g, int64_t ld_g, int Q, int N,

@@ -1,69 +1,18 @@
 // Gallery search on bf16 rows (include/speechclip_hip.h, "Gallery search, bf16 storage"): sc_search_topk with q and g stored in bf16 -- half the gallery bytes,
 // the product on v_mfma_f32_32x32x16_bf16.
 //   search_bf16_kernel  search_core.h's search_block (one block per (query tile, gallery split), scores kept in accumulators, per-row candidate buffers folded
-//                       into sorted lists by rank) with Bf16Rows below as loading, staging and product: a lane holds 8 consecutive k of its row, one
+//                       into sorted lists by rank) with Bf16Rows (search_rows.h) as loading, staging and product: a lane holds 8 consecutive k of its row, one
 //                       ds_read_b128 supplies its k-group of a 16-wide MFMA step, stage rows are 128 bytes.  The bf16 products are exact in fp32; each (i, j)
 //                       has one fp32 accumulator, E is walked in ascending groups of 16 and never split over blocks.
 // Splits, workspace and the merge of the partial lists are those of search.hip (sc_search_splits, sc_search_workspace_bytes, sc_topk_merge).
 #include "common.h"
 #include "search_core.h"
+#include "search_rows.h"
 #include "../../include/speechclip_hip.h"
 
 namespace {
 
 using namespace search_core;
-
-// bf16 rows on v_mfma_f32_32x32x16_bf16: lane (r, h) supplies A[row r][k = 8 h + 0..7] and B[k = 8 h + 0..7][column r] of a 16-wide step
-struct Bf16Rows {
-    using elem = bf16_t;
-    // LDS row stride in elements: 72 = 144 bytes = 9 sixteen-byte slots.  A ds_read_b128 is served in groups of 16 lanes whose rows cover every residue mod 16
-    // ({0-3, 12-15, 20-27}, {4-11, 16-19, 28-31}, the same for the upper half), and 9 r mod 16 is a bijection of them: sixteen distinct slots, conflict-free.
-    static constexpr int LDT = KC + 8;
-    struct unit { bf16x8_t x; };
-    // 8 consecutive elements of one row from e (a multiple of 8; E % 16 == 0: whole 16-byte units); an absent row reads nothing
-    static __device__ __forceinline__ void load(const bf16_t* __restrict__ row, bool row_ok, int e, int E, unit& u) {
-        const bf16x8_t z = {0, 0, 0, 0, 0, 0, 0, 0};
-        u.x = row_ok && e < E ? *(const bf16x8_t*)(row + e) : z;
-    }
-    static __device__ __forceinline__ void store(bf16_t* dst, const unit& u) { *(bf16x8_t*)dst = u.x; }
-    // rq / rg: this lane's row of the wave's first query / gallery tile in the stage images; e0: the stage's first element
-    template <int WQ>
-    static __device__ __forceinline__ void stage(f32x16_t (&acc)[WQ][2], const bf16_t* rq, const bf16_t* rg, int h, int e0, int E) {
-        const bf16_t* aq = rq + 8 * h;
-        const bf16_t* bg = rg + 8 * h;
-        if (e0 + KC <= E) {                              // a whole stage: straight-line code, the fragment reads run ahead of the MFMAs
-            bf16x8_t a8[KC / 16][WQ], b8[KC / 16][2];
-#pragma unroll
-            for (int g16 = 0; g16 < KC / 16; ++g16) {
-#pragma unroll
-                for (int a = 0; a < WQ; ++a) a8[g16][a] = *(const bf16x8_t*)(aq + a * 32 * LDT + 16 * g16);
-#pragma unroll
-                for (int b = 0; b < 2; ++b) b8[g16][b] = *(const bf16x8_t*)(bg + b * 32 * LDT + 16 * g16);
-            }
-#pragma unroll
-            for (int g16 = 0; g16 < KC / 16; ++g16)
-#pragma unroll
-                for (int a = 0; a < WQ; ++a)
-#pragma unroll
-                    for (int b = 0; b < 2; ++b) acc[a][b] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a8[g16][a], b8[g16][b], acc[a][b], 0, 0, 0);
-        } else {                                         // the last stage of a row: E % 16 == 0, so only whole groups of 16, and none beyond E
-#pragma unroll
-            for (int g16 = 0; g16 < KC / 16; ++g16) {
-                if (e0 + 16 * g16 < E) {
-                    bf16x8_t a8[WQ], b8[2];
-#pragma unroll
-                    for (int a = 0; a < WQ; ++a) a8[a] = *(const bf16x8_t*)(aq + a * 32 * LDT + 16 * g16);
-#pragma unroll
-                    for (int b = 0; b < 2; ++b) b8[b] = *(const bf16x8_t*)(bg + b * 32 * LDT + 16 * g16);
-#pragma unroll
-                    for (int a = 0; a < WQ; ++a)
-#pragma unroll
-                        for (int b = 0; b < 2; ++b) acc[a][b] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a8[a], b8[b], acc[a][b], 0, 0, 0);
-                }
-            }
-        }
-    }
-};
 
 template <int WQ, int KL>
 __global__ __launch_bounds__(256) void search_bf16_kernel(const bf16_t* __restrict__ q, int64_t ld_q, const bf16_t* __restrict__ g, int64_t ld_g, int Q, int N,

@@ -143,9 +143,11 @@ class KWClipBase(BaseLightningModel):
             raise ValueError("give exactly one of images, sents, wav, with at least one item")
         return index
 
-    def search(self, index: EmbeddingIndex, k: int, images=None, sents=None, wav=None):
-        """The k nearest items of `index` for every query of one modality -> (scores f32 [Q, k], positions i64 [Q, k], ids): EmbeddingIndex.search."""
-        return index.search(self._embed(images=images, sents=sents, wav=wav), k)
+    def search(self, index: EmbeddingIndex, k: int, images=None, sents=None, wav=None, distinct: bool = False, exclude=None):
+        """The k nearest items of `index` for every query of one modality -> (scores f32 [Q, k], positions i64 [Q, k], ids): EmbeddingIndex.search.
+        distinct=True: the k nearest different ids (an index of several captions per image answers with images); exclude: one id per query to leave out
+        (hard negatives: the nearest items that are not the query's own)."""
+        return index.search(self._embed(images=images, sents=sents, wav=wav), k, distinct=distinct, exclude=exclude)
 
     def forward(self, batch: dict) -> tuple:
         raise NotImplementedError()

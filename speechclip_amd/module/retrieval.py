@@ -62,6 +62,7 @@ class EmbeddingIndex:
         self.segments: List[torch.Tensor] = []
         self.ids: Optional[list] = None            # None: the ids are the running positions
         self._n = 0
+        self._codes = None                         # item codes of the rows (search with distinct / exclude), derived from ids
 
     def __len__(self) -> int:
         return self._n
@@ -100,15 +101,34 @@ class EmbeddingIndex:
         if n:
             self.segments.append(rows)
             self._n += n
+        self._codes = None
         return self
 
-    def search(self, queries: torch.Tensor, k: int):
-        """-> (scores f32 [Q, k] descending, positions i64 [Q, k], ids): ids[i][r] is the stored id of positions[i, r] (the position itself without ids)."""
+    def _item_codes(self):
+        """-> (one int32 device tensor of item codes per segment, {id: code} or None, number of codes).  Equal ids share a code, assigned in first-seen
+        order; without ids the code is the position.  Derived from `ids`, built on first use and dropped by `add`; never stored."""
+        if self._codes is None:
+            table = None if self.ids is None else {}
+            codes = list(range(self._n)) if table is None else [table.setdefault(x, len(table)) for x in self.ids]
+            segs, at = [], 0
+            for seg in self.segments:
+                segs.append(torch.tensor(codes[at:at + seg.shape[0]], dtype=torch.int32, device=seg.device))
+                at += seg.shape[0]
+            self._codes = (segs, table, self._n if table is None else len(table))
+        return self._codes
+
+    def search(self, queries: torch.Tensor, k: int, distinct: bool = False, exclude: Optional[Sequence[Hashable]] = None):
+        """-> (scores f32 [Q, k] descending, positions i64 [Q, k], ids): ids[i][r] is the stored id of positions[i, r] (the position itself without ids).
+        distinct=True: the k nearest DIFFERENT ids, each by its best row (rows that share an id are one item; k <= the number of different ids).
+        exclude: one id per query (a sequence of len(queries)); rows carrying it are left out of that query's result -- None, or an id the index does not
+        hold, leaves out nothing.  With both defaults this is the plain search (sc_search_topk); otherwise sc_search_items, same scores and order."""
         from .. import ops
         k = int(k)
         dev = self._device()
         if not 1 <= k <= min(128, max(self._n, 1)) or self._n == 0:
             raise ValueError(f"k={k} must be in [1, min(128, {self._n} stored rows)]")
+        if distinct or exclude is not None:
+            return self._search_items(queries, k, bool(distinct), exclude, dev)
         q = self._rows(queries)
         search_topk = ops.search_topk_bf16 if self.storage == "bf16" else ops.search_topk
         parts_v, parts_i, base = [], [], 0
@@ -124,9 +144,47 @@ class EmbeddingIndex:
             scores, pos = parts_v[0], parts_i[0]
         else:
             scores, pos = ops.topk_merge(torch.cat(parts_v, 1), torch.cat(parts_i, 1), k)
+        return scores, pos, self._ids_of(pos)
+
+    def _ids_of(self, pos: torch.Tensor) -> list:
         host = pos.cpu().tolist()
-        ids = host if self.ids is None else [[self.ids[p] if p >= 0 else None for p in row] for row in host]
-        return scores, pos, ids
+        return host if self.ids is None else [[self.ids[p] if p >= 0 else None for p in row] for row in host]
+
+    def _search_items(self, queries, k: int, distinct: bool, exclude, dev):
+        """search with distinct / exclude: every segment through sc_search_items[_bf16] with its item codes, partial lists joined by sc_topk_merge_items
+        (exact: a segment is a split).  The arguments are checked on the host before anything runs."""
+        from .. import ops
+        if exclude is not None:
+            exclude = exclude.detach().cpu().tolist() if torch.is_tensor(exclude) else list(exclude)
+            if len(exclude) != len(queries):
+                raise ValueError(f"{len(exclude)} exclude ids for {len(queries)} queries")
+        codes, table, n_ids = self._item_codes()
+        if distinct and k > min(128, n_ids):
+            raise ValueError(f"k={k} must be in [1, min(128, {n_ids} different ids)] with distinct=True")
+        q = self._rows(queries)
+        skip = None
+        if exclude is not None:
+            if table is None:                      # no ids: the id of a row is its position
+                host = [x if isinstance(x, int) and 0 <= x < self._n else -1 for x in exclude]
+            else:
+                host = [-1 if x is None else table.get(x, -1) for x in exclude]
+            skip = torch.tensor(host, dtype=torch.int32, device=dev)
+        search_items = ops.search_items_bf16 if self.storage == "bf16" else ops.search_items
+        parts, base = [], 0
+        for seg, code in zip(self.segments, codes):
+            kk = min(k, seg.shape[0])
+            v, i, c = search_items(q, seg, kk, code, q_skip=skip, distinct=distinct, idx_base=base)
+            if kk < k:                             # a segment shorter than k: padded with entries that take no part in the merge
+                v = torch.cat([v, torch.full((q.shape[0], k - kk), float("-inf"), device=dev)], 1)
+                i = torch.cat([i, torch.full((q.shape[0], k - kk), -1, device=dev, dtype=torch.int64)], 1)
+                c = torch.cat([c, torch.full((q.shape[0], k - kk), -1, device=dev, dtype=torch.int32)], 1)
+            parts.append((v, i, c))
+            base += seg.shape[0]
+        if len(parts) == 1:
+            scores, pos, _ = parts[0]
+        else:
+            scores, pos, _ = ops.topk_merge_items(*(torch.cat(t, 1) for t in zip(*parts)), k, distinct)
+        return scores, pos, self._ids_of(pos)
 
     def astype(self, storage: str) -> "EmbeddingIndex":
         """A new index with the same segment boundaries and ids in the other storage: fp32 -> bf16 rounds the stored rows (to nearest even), bf16 -> fp32

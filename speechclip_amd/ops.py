@@ -1105,6 +1105,59 @@ def topk_merge(vals, idx, k):
     return out_v, out_i
 
 
+# ---- gallery search by item (search_items.hip) ----
+def _search_items(entry, dtype, q, g, k, g_item, q_skip, distinct, n_split, idx_base, workspace):
+    """The two storage formats of the id-aware search: _search_topk plus the item codes of the gallery rows, the queries' skip codes and the third output."""
+    _need_cuda(q, g, g_item)
+    assert q.dtype == dtype and g.dtype == dtype and q.dim() == 2 and g.dim() == 2 and q.stride(1) == 1 and g.stride(1) == 1
+    assert q.shape[1] == g.shape[1], (q.shape, g.shape)
+    Q, E = q.shape
+    N, k = g.shape[0], int(k)
+    assert g_item.dtype == torch.int32 and g_item.shape == (N,) and g_item.is_contiguous(), (g_item.dtype, g_item.shape)
+    if q_skip is not None:
+        _need_cuda(q_skip)
+        assert q_skip.dtype == torch.int32 and q_skip.shape == (Q,) and q_skip.is_contiguous(), (q_skip.dtype, q_skip.shape)
+    vals = torch.empty(Q, k, device=q.device, dtype=torch.float32)
+    idx = torch.empty(Q, k, device=q.device, dtype=torch.int64)
+    items = torch.empty(Q, k, device=q.device, dtype=torch.int32)
+    nbytes = lib().sc_search_items_workspace_bytes(Q, N, k, int(n_split))
+    if workspace is None and nbytes > 0:
+        workspace = torch.empty(nbytes, device=q.device, dtype=torch.uint8)
+    assert workspace is None or (workspace.is_cuda and workspace.numel() * workspace.element_size() >= nbytes)
+    check(getattr(lib(), entry)(ptr(q), q.stride(0), ptr(g), g.stride(0), Q, N, E, k, int(n_split), int(idx_base), ptr(g_item), ptr(q_skip), int(bool(distinct)),
+                                ptr(vals), ptr(idx), ptr(items), ptr(workspace), stream()), entry)
+    return vals, idx, items
+
+
+def search_items(q, g, k, g_item, q_skip=None, distinct=False, n_split=0, idx_base=0, workspace=None):
+    """search_topk by item: g_item i32 [N] gives every gallery row an item code (>= 0), q_skip i32 [Q] (or None) names the item each query leaves out (< 0:
+    none) -> (vals f32 [Q, k], idx i64 [Q, k], items i32 [Q, k]).  distinct=False: the first k rows whose item is not the query's skip code; distinct=True:
+    the first k ITEMS, each by its best row.  Scores, order, splits and idx_base are search_topk's; missing slots hold -inf / -1 / -1 (sc_search_items).
+    `workspace`: a caller's uint8 buffer of at least sc_search_items_workspace_bytes; default: allocated here."""
+    return _search_items("sc_search_items", torch.float32, q, g, k, g_item, q_skip, distinct, n_split, idx_base, workspace)
+
+
+def search_items_bf16(q, g, k, g_item, q_skip=None, distinct=False, n_split=0, idx_base=0, workspace=None):
+    """search_items on bf16 rows: search_topk_bf16's scores under the same selection (sc_search_items_bf16)."""
+    return _search_items("sc_search_items_bf16", bf16, q, g, k, g_item, q_skip, distinct, n_split, idx_base, workspace)
+
+
+def topk_merge_items(vals, idx, items, k, distinct):
+    """vals f32 [Q, L], idx i64 [Q, L], items i32 [Q, L]: L candidates per row in any order -> the first k by (value descending, idx ascending), with
+    distinct=True only the first of each item code; entries with idx < 0 or a NaN value take no part, missing slots are -inf / -1 / -1
+    (sc_topk_merge_items)."""
+    _need_cuda(vals, idx, items)
+    assert vals.dtype == torch.float32 and idx.dtype == torch.int64 and items.dtype == torch.int32 and vals.dim() == 2 and vals.shape == idx.shape == items.shape
+    vals, idx, items = vals.contiguous(), idx.contiguous(), items.contiguous()
+    Q, L = vals.shape
+    out_v = torch.empty(Q, int(k), device=vals.device, dtype=torch.float32)
+    out_i = torch.empty(Q, int(k), device=vals.device, dtype=torch.int64)
+    out_c = torch.empty(Q, int(k), device=vals.device, dtype=torch.int32)
+    check(lib().sc_topk_merge_items(ptr(vals), ptr(idx), ptr(items), Q, L, int(k), int(bool(distinct)), ptr(out_v), ptr(out_i), ptr(out_c), stream()),
+          "sc_topk_merge_items")
+    return out_v, out_i, out_c
+
+
 # ---- cascaded tail, training (train_cascaded.hip) ----
 def attn_small_bwd(qkv16, dout, B, L, H, causal=True):
     """qkv bf16 [B*L, 3*H*64] (saved by the forward), dout f32 [B*L, H*64] -> dqkv f32 [B*L, 3*H*64]."""
