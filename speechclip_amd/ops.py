@@ -509,7 +509,8 @@ def posconv_packed(x, valid_i32, row_off_i32, wg, bias, gamma, beta, B, rows_max
     conv = torch.empty(total_rows * D, device=x.device, dtype=bf16)
     rc = lib().sc_posconv_conv_packed(ptr(x), ptr(valid_i32), ptr(row_off_i32), ptr(wg), ptr(conv), B, rows_max, D, G, Kw, stream())
     if rc == 1:
-        raise _lib.SpeechClipHipError(f"packed batches need the windowed positional-conv kernel (D/G in 32/48/64), got D/G = {cg}")
+        raise _lib.SpeechClipHipError("packed batches need the windowed positional-conv kernel (D/G in 32/48/64 and Kw * D/G a multiple of 64), "
+                                      f"got D/G = {cg}, Kw = {Kw}")
     check(rc, "sc_posconv_conv_packed")
     if out is None:
         out = torch.empty(total_rows, D, device=x.device, dtype=torch.float32 if out_f32 else bf16)
@@ -1690,7 +1691,8 @@ def posconv_conv_packed(x, lim_i32, row_off_i32, wg, B, rows_max, total_rows, D,
     conv = torch.empty(total_rows * D, device=x.device, dtype=bf16)
     rc = lib().sc_posconv_conv_packed(ptr(x), ptr(lim_i32), ptr(row_off_i32), ptr(wg), ptr(conv), B, rows_max, D, G, Kw, stream())
     if rc == 1:
-        raise _lib.SpeechClipHipError(f"packed batches need the windowed positional-conv kernel (D/G in 32/48/64), got D/G = {D // G}")
+        raise _lib.SpeechClipHipError("packed batches need the windowed positional-conv kernel (D/G in 32/48/64 and Kw * D/G a multiple of 64), "
+                                      f"got D/G = {D // G}, Kw = {Kw}")
     check(rc, "sc_posconv_conv_packed")
     return conv
 
