@@ -321,6 +321,12 @@ int sc_cosine_scores(const float* a, const float* emb, void* workspace, float* o
 /* sc_cosine_refine: for score matrices produced on the MFMA path (three-term bf16 split GEMM, ~1e-5 accurate): every entry within `delta` of its
  *   row maximum is recomputed in fp32 as (a . e) / (max(|a|,eps) max(|e|,eps)), so the arg-max is decided by fp32 arithmetic (kwClip.py:889-909). */
 int sc_cosine_refine(float* scores, const float* a, const float* emb, int R, int V, int E, float delta, float eps, void* stream);
+/* sc_cosine_refine_masked: the same for a quantiser that masks sub-words afterwards (sc_vq_fwd's host_mask_ids, at most 8): the refined set is
+ *   every UNMASKED entry within `delta` of the row's maximum over the UNMASKED columns; masked columns are neither read for the maximum nor
+ *   rewritten.  Candidates are chosen from the values on entry, however many there are, and the result is bitwise repeatable.
+ *   sc_cosine_refine is the n_mask = 0 case. */
+int sc_cosine_refine_masked(float* scores, const float* a, const float* emb, int R, int V, int E, float delta, float eps,
+                            const int32_t* host_mask_ids, int n_mask, void* stream);
 int64_t sc_vq_workspace_bytes(int R, int V);
 int sc_vq_fwd(const float* scores, int64_t* targets, float* stats2, float* ent_per_t, void* workspace, int R, int K, int V,
               const int32_t* host_mask_ids, int n_mask, void* stream);

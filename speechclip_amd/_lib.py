@@ -147,6 +147,7 @@ def _declare(L):
         "sc_debug_vendor_stream_slot": ([P], c_int),
         "sc_split_hilo_bf16": ([P, L64, P, L64, I, I, P], c_int),
         "sc_cosine_refine": ([P, P, P, I, I, I, F, F, P], c_int),
+        "sc_cosine_refine_masked": ([P, P, P, I, I, I, F, F, P, I, P], c_int),
         "sc_attn_small_bwd": ([P, P, P, I, I, I, I, I, P], c_int),
         "sc_quickgelu_f32": ([P, P, L64, I, I, P], c_int),
         "sc_vq_st_bwd": ([P, P, P, I, I, F, P, I, P], c_int),

@@ -70,48 +70,6 @@ __global__ __launch_bounds__(256) void cosine_tile_kernel(const float* __restric
 }
 
 
-// Exact re-evaluation of the near-maximal entries of a score row.  The MFMA path (sc_gemm_bf16 on three-term bf16 splits of the normalised
-// operands) is accurate to ~1e-5; every entry within `delta` of the row maximum is recomputed here as (a . e) inv|a| inv|e| in fp32, so the
-// arg-max -- the sub-word the quantiser picks -- is decided by fp32 arithmetic as in the reference.  One block per row.
-constexpr int MAXCAND = 128;
-__global__ __launch_bounds__(256) void cosine_refine_kernel(float* __restrict__ cosv, const float* __restrict__ a, const float* __restrict__ e, int V, int E,
-                                                            float delta, float eps) {
-    __shared__ float s_red[8];
-    __shared__ int s_cand[MAXCAND];
-    __shared__ int s_n;
-    const int r = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
-    float* row = cosv + (int64_t)r * V;
-    const float* ar = a + (int64_t)r * E;
-    float mx = -INFINITY;
-    for (int v = tid; v < V; v += 256) mx = fmaxf(mx, row[v]);
-    mx = wave_max(mx);
-    if (lane == 0) s_red[wv] = mx;
-    if (tid == 0) s_n = 0;
-    __syncthreads();
-    mx = fmaxf(fmaxf(s_red[0], s_red[1]), fmaxf(s_red[2], s_red[3]));
-    for (int v = tid; v < V; v += 256)
-        if (row[v] >= mx - delta) { const int i = atomicAdd(&s_n, 1); if (i < MAXCAND) s_cand[i] = v; }
-    float qa = 0.f;
-    for (int k = tid; k < E; k += 256) qa += ar[k] * ar[k];
-    qa = wave_sum(qa);
-    __syncthreads();
-    if (lane == 0) s_red[4 + wv] = qa;
-    __syncthreads();
-    const float inv_a = 1.0f / fmaxf(sqrtf(s_red[4] + s_red[5] + s_red[6] + s_red[7]), eps);
-    const int n = s_n < MAXCAND ? s_n : MAXCAND;
-    for (int c = 0; c < n; ++c) {
-        const int v = s_cand[c];
-        const float* ev = e + (int64_t)v * E;
-        float d = 0.f, q = 0.f;
-        for (int k = tid; k < E; k += 256) { const float x = ev[k]; d = fmaf(ar[k], x, d); q = fmaf(x, x, q); }
-        d = wave_sum(d); q = wave_sum(q);
-        __syncthreads();
-        if (lane == 0) { s_red[wv] = d; s_red[4 + wv] = q; }
-        __syncthreads();
-        if (tid == 0) row[v] = (s_red[0] + s_red[1] + s_red[2] + s_red[3]) * inv_a * (1.0f / fmaxf(sqrtf(s_red[4] + s_red[5] + s_red[6] + s_red[7]), eps));
-    }
-}
-
 __device__ __forceinline__ bool is_masked(int v, const int* msk, int nmsk) {
     for (int i = 0; i < nmsk; ++i)
         if (msk[i] == v) return true;
@@ -119,6 +77,90 @@ __device__ __forceinline__ bool is_masked(int v, const int* msk, int nmsk) {
 }
 
 struct MaskIds { int n; int id[8]; };
+
+// Exact re-evaluation of the near-maximal entries of a score row.  The MFMA path (sc_gemm_bf16 on three-term bf16 splits of the normalised
+// operands) is accurate to ~1e-5; every UNMASKED entry within `delta` of the row's maximum OVER THE UNMASKED columns is recomputed here as
+// (a . e) inv|a| inv|e| in fp32, so the arg-max the quantiser takes after masking -- the sub-word it picks -- is decided by fp32 arithmetic as
+// in the reference.  Masked columns never decide the threshold and are never rewritten.  One block per row.
+// Candidates are chosen from the values the row held on entry, and there is no cap on their number: up to MAXCAND of them are collected in one
+// sweep (the usual case; the order the atomic hands out does not reach the result, every candidate's value is computed on its own); a row with
+// more is walked in index order, 256 columns at a time, each chunk's candidates compacted in order and refined before the next chunk is read
+// (an entry is rewritten only after its own chunk was tested, so the test still sees the value on entry).  Bitwise repeatable either way.
+constexpr int MAXCAND = 128;
+__device__ __forceinline__ void refine_entry(float* __restrict__ row, const float* __restrict__ ar, const float* __restrict__ e, int v, int E, float inv_a,
+                                             float eps, float* s_red) {
+    const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+    const float* ev = e + (int64_t)v * E;
+    float d = 0.f, q = 0.f;
+    for (int k = tid; k < E; k += 256) { const float x = ev[k]; d = fmaf(ar[k], x, d); q = fmaf(x, x, q); }
+    d = wave_sum(d); q = wave_sum(q);
+    __syncthreads();
+    if (lane == 0) { s_red[wv] = d; s_red[4 + wv] = q; }
+    __syncthreads();
+    if (tid == 0) row[v] = (s_red[0] + s_red[1] + s_red[2] + s_red[3]) * inv_a * (1.0f / fmaxf(sqrtf(s_red[4] + s_red[5] + s_red[6] + s_red[7]), eps));
+}
+
+__global__ __launch_bounds__(256) void cosine_refine_kernel(float* __restrict__ cosv, const float* __restrict__ a, const float* __restrict__ e, int V, int E,
+                                                            float delta, float eps, MaskIds mk) {
+    __shared__ float s_red[8];
+    __shared__ int s_cand[256];
+    __shared__ int s_wcnt[4];
+    __shared__ int s_n;
+    const int r = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+    float* row = cosv + (int64_t)r * V;
+    const float* ar = a + (int64_t)r * E;
+    // The sweep for the maximum runs over every column, as without a mask; only when a masked column holds (or ties) that maximum -- block-uniform, and rare on
+    // real scores -- does the maximum over the unmasked columns need a sweep of its own.
+    float mx = -INFINITY;
+    for (int v = tid; v < V; v += 256) mx = fmaxf(mx, row[v]);
+    mx = wave_max(mx);
+    if (lane == 0) s_red[wv] = mx;
+    if (tid == 0) s_n = 0;
+    __syncthreads();
+    mx = fmaxf(fmaxf(s_red[0], s_red[1]), fmaxf(s_red[2], s_red[3]));
+    float masked_mx = -INFINITY;
+    for (int i = 0; i < mk.n; ++i)
+        if (mk.id[i] >= 0 && mk.id[i] < V) masked_mx = fmaxf(masked_mx, row[mk.id[i]]);
+    if (masked_mx >= mx) {
+        mx = -INFINITY;
+        for (int v = tid; v < V; v += 256)
+            if (!is_masked(v, mk.id, mk.n)) mx = fmaxf(mx, row[v]);
+        mx = wave_max(mx);
+        __syncthreads();                                     // every thread has read the first maximum
+        if (lane == 0) s_red[wv] = mx;
+        __syncthreads();
+        mx = fmaxf(fmaxf(s_red[0], s_red[1]), fmaxf(s_red[2], s_red[3]));
+    }
+    const float thr = mx - delta;
+    for (int v = tid; v < V; v += 256)
+        if (row[v] >= thr && !is_masked(v, mk.id, mk.n)) { const int i = atomicAdd(&s_n, 1); if (i < MAXCAND) s_cand[i] = v; }
+    float qa = 0.f;
+    for (int k = tid; k < E; k += 256) qa += ar[k] * ar[k];
+    qa = wave_sum(qa);
+    __syncthreads();
+    if (lane == 0) s_red[4 + wv] = qa;
+    __syncthreads();
+    const float inv_a = 1.0f / fmaxf(sqrtf(s_red[4] + s_red[5] + s_red[6] + s_red[7]), eps);
+    const int total = s_n;                                   // block-uniform: read after the barrier, never written again
+    if (total <= MAXCAND) {
+        for (int c = 0; c < total; ++c) refine_entry(row, ar, e, s_cand[c], E, inv_a, eps, s_red);
+        return;
+    }
+    for (int base = 0; base < V; base += 256) {              // nothing of the row has been rewritten yet
+        const int v = base + tid;
+        const bool c = v < V && row[v] >= thr && !is_masked(v, mk.id, mk.n);
+        const unsigned long long bal = __ballot(c);
+        __syncthreads();                                     // the previous chunk's s_cand / s_wcnt are no longer read
+        if (lane == 0) s_wcnt[wv] = __popcll(bal);
+        __syncthreads();
+        int off = 0;
+        for (int w = 0; w < wv; ++w) off += s_wcnt[w];
+        const int n = s_wcnt[0] + s_wcnt[1] + s_wcnt[2] + s_wcnt[3];
+        if (c) s_cand[off + __popcll(bal & ((1ull << lane) - 1ull))] = v;
+        __syncthreads();
+        for (int i = 0; i < n; ++i) refine_entry(row, ar, e, s_cand[i], E, inv_a, eps, s_red);
+    }
+}
 
 // one block per row: arg-max (first index on ties), row max, log-sum-exp, entropy -sum p log(p + 1e-9)
 __global__ __launch_bounds__(256) void vq_row_kernel(const float* __restrict__ x, int64_t* __restrict__ targets, float* __restrict__ rmax,
@@ -146,6 +188,7 @@ __global__ __launch_bounds__(256) void vq_row_kernel(const float* __restrict__ x
     best = s_val[0]; bi = s_idx[0];
     for (int w = 1; w < 4; ++w)
         if (s_val[w] > best || (s_val[w] == best && s_idx[w] < bi)) { best = s_val[w]; bi = s_idx[w]; }
+    if (bi == 0x7fffffff) bi = 0;          // no column compares (an all-NaN row): target 0, as vq_noisy_argmax_kernel; hist[bi] stays inside [0, V)
     float se = 0.f;
     for (int v = tid; v < V; v += 256)
         if (!is_masked(v, mk.id, mk.n)) se += __expf(row[v] - best);
@@ -259,12 +302,30 @@ extern "C" int sc_cosine_scores(const float* a, const float* emb, void* workspac
 
 static int vq_nsplit(int R) { return R >= 1024 ? 32 : (R >= 64 ? 8 : 1); }
 
-extern "C" int sc_cosine_refine(float* scores, const float* a, const float* emb, int R, int V, int E, float delta, float eps, void* stream) {
+// true when the ids cover every column of [0, V): nothing is left to compare (ids outside [0, V) and repeats do not count)
+static bool mask_covers_all(const int32_t* ids, int n_mask, int V) {
+    if (V > 8) return false;
+    int seen = 0;
+    for (int i = 0; i < n_mask; ++i)
+        if (ids[i] >= 0 && ids[i] < V) seen |= 1 << ids[i];
+    return seen == (1 << V) - 1;
+}
+
+extern "C" int sc_cosine_refine_masked(float* scores, const float* a, const float* emb, int R, int V, int E, float delta, float eps,
+                                       const int32_t* host_mask_ids, int n_mask, void* stream) {
     SC_CHECK_ARG(R >= 0 && V > 0 && E > 0 && delta >= 0.f, "sc_cosine_refine: bad arguments");
+    SC_CHECK_ARG(n_mask >= 0 && n_mask <= 8 && (n_mask == 0 || host_mask_ids), "sc_cosine_refine: at most 8 masked ids (n_mask=%d)", n_mask);
     if (R == 0) return 0;
-    hipLaunchKernelGGL(cosine_refine_kernel, dim3(R), dim3(256), 0, (hipStream_t)stream, scores, a, emb, V, E, delta, eps);
+    MaskIds mk{};
+    mk.n = n_mask;
+    for (int i = 0; i < n_mask; ++i) mk.id[i] = host_mask_ids[i];
+    hipLaunchKernelGGL(cosine_refine_kernel, dim3(R), dim3(256), 0, (hipStream_t)stream, scores, a, emb, V, E, delta, eps, mk);
     SC_CHECK_LAUNCH();
     return 0;
+}
+
+extern "C" int sc_cosine_refine(float* scores, const float* a, const float* emb, int R, int V, int E, float delta, float eps, void* stream) {
+    return sc_cosine_refine_masked(scores, a, emb, R, V, E, delta, eps, nullptr, 0, stream);
 }
 
 extern "C" int64_t sc_vq_workspace_bytes(int R, int V) { return ((int64_t)3 * R + (V + 255) / 256 + (int64_t)V * (1 + vq_nsplit(R))) * 4; }
@@ -273,6 +334,8 @@ extern "C" int sc_vq_fwd(const float* scores, int64_t* targets, float* stats2, f
                          const int32_t* host_mask_ids, int n_mask, void* stream) {
     SC_CHECK_ARG(R > 0 && K > 0 && R % K == 0 && V > 0, "sc_vq_fwd: bad sizes R=%d K=%d V=%d", R, K, V);
     SC_CHECK_ARG(n_mask >= 0 && n_mask <= 8, "sc_vq_fwd: at most 8 masked ids");
+    SC_CHECK_ARG(n_mask == 0 || host_mask_ids, "sc_vq_fwd: null mask ids");
+    SC_CHECK_ARG(!mask_covers_all(host_mask_ids, n_mask, V), "sc_vq_fwd: every id of [0, V=%d) is masked", V);
     MaskIds mk{};
     mk.n = n_mask;
     for (int i = 0; i < n_mask; ++i) mk.id[i] = host_mask_ids[i];

@@ -503,7 +503,7 @@ class KW_CascadedBranch(nn.Module):
         if hasattr(self, "bn_layer"):
             kw = self.bn_layer(kw)
         emb = self.clip.model.token_embedding.weight
-        cos = ops.cosine_scores(kw.reshape(B * K, self.text_dim), emb).view(B, K, emb.shape[0])   # fp32, exact arg-max
+        cos = ops.cosine_scores(kw.reshape(B * K, self.text_dim), emb, mask_ids=(0, 2, 3)).view(B, K, emb.shape[0])   # fp32-exact arg-max over the ids the quantizer keeps
         vq_results = self.vector_quantizer(x=cos)
         assert emb.requires_grad is False
         keywords = self.vector_quantizer.embed(vq_results, emb)
@@ -534,7 +534,7 @@ def _kw_cascaded_forward_train(self, audio_feat: torch.Tensor, audio_len: torch.
         kw = self.bn_layer(kw)
     emb = self.clip.model.token_embedding.weight
     assert emb.requires_grad is False
-    cos = ops.cosine_scores(kw.detach().reshape(B * K, self.text_dim), emb)                     # fp32 [B*K, V]
+    cos = ops.cosine_scores(kw.detach().reshape(B * K, self.text_dim), emb, mask_ids=(0, 2, 3))   # fp32 [B*K, V]; the quantizer's masked ids
     vq_results = self.vector_quantizer(x=cos.view(B, K, emb.shape[0]))
     vq = self.vector_quantizer      # a learnable temperature (vq.temp: "learnable=...") goes in as the parameter itself: KeywordSTFn returns its gradient
     temp = vq.curr_temp if getattr(vq, "temp_type", "") == "learnable" else vq.temperature_value()

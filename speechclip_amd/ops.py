@@ -739,6 +739,7 @@ def kw_affine(x, scale, shift):
 
 
 _COS_TABLES = {}
+COS_REFINE_DELTA = 1e-3            # the MFMA path's refine window below the row maximum (cosine_scores)
 
 
 def _cos_table(emb):
@@ -758,11 +759,17 @@ def _cos_table(emb):
     return tab
 
 
-def cosine_scores(a, emb, eps=1e-8, exact=None):
-    """a f32 [R,E], emb f32 [V,E] -> f32 [R,V] cosine similarities.
-    Large problems (the 49408-entry sub-word table) run on the MFMA GEMM with three-term bf16 splits of the normalised operands (~1e-5
-    accurate) followed by sc_cosine_refine, which recomputes every entry within 1e-3 of its row maximum in fp32 -- the arg-max is decided
-    by fp32 arithmetic either way.  Small problems / `exact=True`: the fp32 SIMT kernel for the whole matrix."""
+def cosine_scores(a, emb, eps=1e-8, exact=None, mask_ids=()):
+    """a f32 [R,E], emb f32 [V,E] -> f32 [R,V] cosine similarities a_r . e_v / (max(|a_r|, eps) max(|e_v|, eps)).
+    Small problems / `exact=True`: the fp32 SIMT kernel for the whole matrix (every entry fp32-accurate; `mask_ids` plays no part).
+    Otherwise (E % 64 == 0, V % 4 == 0, R * V >= 2^22 -- the 49408-entry sub-word table -- or `exact=False`): the MFMA GEMM on three-term
+    bf16 splits of the normalised operands (a_hi.e_hi + a_lo.e_hi + a_hi.e_lo: the dropped a_lo.e_lo and the bf16 roundings of the lo parts
+    are each at most 2^-16 sum|a_n e_n|, 4.6e-5 in all; ~2e-5 is the most the tests provoke), followed by sc_cosine_refine_masked.  The contract of that path (tests/test_cascaded_fwd_parity_gpu.py):
+      * every entry whose column is not in `mask_ids` and whose GEMM value lies within 1e-3 of the row's maximum over the columns not in
+        `mask_ids` is recomputed in fp32, however many there are; every other entry keeps the GEMM's value;
+      * so the arg-max over the columns not in `mask_ids` is decided by fp32 arithmetic, as on the exact path.  `mask_ids` (at most 8) are the
+        ids the quantiser masks AFTERWARDS (sc_vq_fwd); a caller that masks and passes none gets the guarantee for the unmasked arg-max only;
+      * the result is bitwise repeatable."""
     _need_cuda(a, emb)
     a = a.float().contiguous()
     R, E = a.shape
@@ -780,7 +787,9 @@ def cosine_scores(a, emb, eps=1e-8, exact=None):
     gemm(a3, tab, out=out, out_f32=True)
     embf = emb.detach()
     embf = embf if (embf.dtype == torch.float32 and embf.is_contiguous()) else embf.float().contiguous()
-    check(lib().sc_cosine_refine(ptr(out), ptr(a), ptr(embf), R, V, E, 1e-3, eps, stream()), "sc_cosine_refine")
+    ids, ids_p, n_mask = _mask_arg(mask_ids)                  # `ids` owns the host array until the call has returned
+    check(lib().sc_cosine_refine_masked(ptr(out), ptr(a), ptr(embf), R, V, E, COS_REFINE_DELTA, eps, ids_p, n_mask, stream()),
+          "sc_cosine_refine_masked")
     return out
 
 
