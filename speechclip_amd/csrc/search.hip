@@ -1,10 +1,9 @@
 // Gallery search (include/speechclip_hip.h, "Gallery search"): the K nearest gallery rows of every query row WITHOUT the [Q, N] score image.
 //   search_kernel      one block per (query tile, gallery split): fp32 scores on v_mfma_f32_32x32x2_f32 (a k-ordered fmaf chain per (i, j), E walked in
-//                      ascending order, one accumulator chain, no split over E), kept in accumulators; every score is filtered against its row's current
-//                      K-th entry, survivors go to a per-row LDS candidate buffer, and a full buffer is folded into the row's sorted top-K list by RANK in
-//                      the total order (score descending, j ascending) -- the buffer may fill in any order, the list cannot tell.  The block body is
-//                      search_core.h's search_block, shared with the bf16-row kernel of search_bf16.hip; F32Rows (search_rows.h) is the fp32 loading and product.
+//                      ascending order, one accumulator chain, no split over E), kept in accumulators and selected inside the block.  The block body is
+//                      search_core.h's search_block under the plain selection, with F32Rows (search_rows.h) as loading, staging and product.
 //   topk_merge_kernel  L candidates per row -> the first K of that order (the partial lists of the splits, of gallery segments, of ranks).
+// The split rule and the workspace size of all four search entries are here; the entries' host side is search_core.h's search_host.
 // No global atomics; the LDS counters only hand out buffer slots.  Every output element is written once.
 #include "common.h"
 #include "search_core.h"
@@ -22,7 +21,7 @@ template <int WQ, int KL>
 __global__ __launch_bounds__(256) void search_kernel(const float* __restrict__ q, int64_t ld_q, const float* __restrict__ g, int64_t ld_g, int Q, int N,
                                                       int E, int K, int per, int S, int64_t idx_base, float* __restrict__ out_v,
                                                       int64_t* __restrict__ out_i) {
-    search_block<F32Rows, WQ, KL>(q, ld_q, g, ld_g, Q, N, E, K, per, S, idx_base, out_v, out_i);
+    search_block<F32Rows, false, WQ, KL>(q, ld_q, g, ld_g, Q, N, E, K, per, S, idx_base, nullptr, nullptr, 0, out_v, out_i, nullptr);
 }
 
 // K rounds of a block-wide arg-max over L (value, id) pairs; round p picks the first pair strictly after round p-1's pick in (value descending, id
@@ -99,32 +98,6 @@ extern "C" int sc_topk_merge(const float* vals_in, const int64_t* idx_in, int Q,
 
 extern "C" int sc_search_topk(const float* q, int64_t ld_q, const float* g, int64_t ld_g, int Q, int64_t N, int E, int K, int n_split, int64_t idx_base,
                               float* vals, int64_t* idx, void* workspace, void* stream) {
-    SC_CHECK_ARG(E >= 4 && E <= 1024 && E % 4 == 0, "sc_search_topk: E=%d must be a multiple of 4 in [4, 1024]", E);
-    SC_CHECK_ARG(ld_q >= E && ld_g >= E && ld_q % 4 == 0 && ld_g % 4 == 0, "sc_search_topk: ld_q=%lld / ld_g=%lld must be multiples of 4 and >= E=%d",
-                 (long long)ld_q, (long long)ld_g, E);
-    SC_CHECK_ARG((((uintptr_t)q | (uintptr_t)g) & 15) == 0, "sc_search_topk: q and g must be 16-byte aligned");
-    SC_CHECK_ARG(K >= 1 && K <= 128, "sc_search_topk: K=%d must be in [1, 128]", K);
-    SC_CHECK_ARG(N < ((int64_t)1 << 31), "sc_search_topk: N=%lld must be below 2^31", (long long)N);
-    SC_CHECK_ARG(K <= N, "sc_search_topk: K=%d exceeds N=%lld", K, (long long)N);
-    SC_CHECK_ARG(n_split >= 0 && n_split <= 1024, "sc_search_topk: n_split=%d must be in [0, 1024] (0 = auto)", n_split);
-    SC_CHECK_ARG(Q >= 0, "sc_search_topk: Q=%d is negative", Q);
-    if (Q == 0) return 0;
-    SC_CHECK_ARG(q && g && vals && idx, "sc_search_topk: null operand");
-    const int S = n_split ? n_split : sc_search_splits(Q, N, K);
-    SC_CHECK_ARG(S == 1 || workspace, "sc_search_topk: %d splits need a workspace (sc_search_workspace_bytes)", S);
-    const int per = (int)((N + S - 1) / S);
-    int64_t* wi = (int64_t*)workspace;                       // [Q][S][K] i64, then [Q][S][K] f32
-    float* wv = (float*)(wi + (int64_t)Q * S * K);
-    float* ov = S == 1 ? vals : wv;
-    int64_t* oi = S == 1 ? idx : wi;
-    const int bq = query_rows_per_block(Q, K);
-    const dim3 grid((unsigned)((Q + bq - 1) / bq), (unsigned)S);
-    hipStream_t st = (hipStream_t)stream;
-#define SC_SEARCH_LAUNCH(WQ, KL) hipLaunchKernelGGL((search_kernel<WQ, KL>), grid, dim3(256), 0, st, q, ld_q, g, ld_g, Q, (int)N, E, K, per, S, idx_base, ov, oi)
-    if (bq == 128) { if (K <= 16) SC_SEARCH_LAUNCH(2, 16); else SC_SEARCH_LAUNCH(2, 64); }
-    else           { if (K <= 16) SC_SEARCH_LAUNCH(1, 16); else SC_SEARCH_LAUNCH(1, 128); }
-#undef SC_SEARCH_LAUNCH
-    SC_CHECK_LAUNCH();
-    if (S > 1) return sc_topk_merge(wv, wi, Q, S * K, K, vals, idx, stream);
-    return 0;
+    return search_host<F32Rows, false>("sc_search_topk", 4, 4, {search_kernel<2, 16>, search_kernel<2, 64>, search_kernel<1, 16>, search_kernel<1, 128>}, q, ld_q,
+                                       g, ld_g, Q, N, E, K, n_split, idx_base, nullptr, nullptr, 0, vals, idx, nullptr, workspace, stream);
 }

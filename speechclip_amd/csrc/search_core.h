@@ -1,10 +1,23 @@
-// Gallery search, the part that does not depend on the operand format (include/speechclip_hip.h, "Gallery search" and "Gallery search, bf16 storage"):
-// the block of search_kernel (search.hip, fp32 rows) and of search_bf16_kernel (search_bf16.hip, bf16 rows).  One 256-thread block per (query tile, gallery
-// split), waves 2 x 2 over 64 WQ query rows x 128 gallery rows; scores stay in the 32 x 32 MFMA accumulators; every score is filtered against its row's
-// current K-th entry, survivors go to a per-row LDS candidate buffer, and a full buffer is folded into the row's sorted top-K list by RANK in the total order
-// (score descending, j ascending) -- the buffer may fill in any order, the list cannot tell.  No global atomics; the LDS counters only hand out buffer slots.
+// Gallery search, everything that does not depend on the operand format (include/speechclip_hip.h, "Gallery search", "Gallery search, bf16 storage" and
+// "Gallery search by item"): ONE block body and ONE host driver for the four entries.
+//   search_block      the block of search_kernel (search.hip, fp32 rows), search_bf16_kernel (search_bf16.hip, bf16 rows) and search_items_kernel
+//                     (search_items.hip, both formats).  One 256-thread block per (query tile, gallery split), waves 2 x 2 over 64 WQ query rows x 128 gallery
+//                     rows; scores stay in the 32 x 32 MFMA accumulators; every score is filtered against its row's current K-th entry, survivors go to a
+//                     per-row LDS candidate buffer, and a full buffer is folded into the row's sorted top-K list by RANK in the total order (score descending,
+//                     j ascending) -- the buffer may fill in any order, the list cannot tell.  No global atomics; the LDS counters only hand out buffer slots.
+//   search_host       argument rules, split and workspace arithmetic, launch and merge of sc_search_topk, sc_search_topk_bf16, sc_search_items and
+//                     sc_search_items_bf16.
+// Two SELECTIONS, chosen at compile time by ITEMS:
+//   ITEMS == false    the plain one: the first K (score, j) pairs.
+//   ITEMS == true     by item: a score is pushed only if it is ELIGIBLE (its row's item code g_item[j] differs from the query's skip code) and before its row's
+//                     K-th entry; with `distinct` the rank fold first drops every entry of list + buffer that is DOMINATED (another entry with the same item
+//                     code is before it) and ranks the survivors among the survivors; a third output carries the item codes.  The list and the buffer hold
+//                     (score, j) either way: an entry's item code is g_item[j], read from global memory (N * 4 bytes, L2-resident) only inside a `distinct`
+//                     fold and for the output, so both selections have the same four (WQ, list capacity) instantiations and LDS sizes (+ 4 bytes of skip
+//                     code per query row by item).
+// Everything by item stands under `if constexpr (ITEMS)`, its LDS array included: the plain instantiations hold none of it.
 //
-// The operand format OP supplies what differs -- loading, staging and the product:
+// The operand format OP (search_rows.h) supplies what differs between fp32 and bf16 rows -- loading, staging and the product:
 //   elem                   storage type of a q / g element
 //   LDT                    LDS row stride of a stage image, in elements, chosen so that the fragment reads (ds_read_b128) are conflict-free
 //   unit, load, store      8 consecutive elements of one row: global -> registers (an absent row or e >= E reads nothing and holds zeros) -> stage image
@@ -12,6 +25,7 @@
 // Both MFMAs used (32x32x2_f32, 32x32x16_bf16) leave accumulator x of lane (r, h) = (lane & 31, lane >> 5) at (row (x & 3) + 8 (x >> 2) + 4 h, column r).
 #pragma once
 #include "common.h"
+#include "../../include/speechclip_hip.h"
 #include <limits.h>
 
 namespace search_core {
@@ -23,13 +37,18 @@ constexpr int NO_J = INT_MAX;    // empty list slot: (-inf, NO_J) comes after ev
 // (av, aj) strictly before (bv, bj) in (score descending, j ascending).  A NaN score is before nothing and nothing is before it.
 __device__ __forceinline__ bool before(float av, int aj, float bv, int bj) { return av > bv || (av == bv && aj < bj); }
 
+__device__ __forceinline__ uint64_t low_bits(int n) { return n >= 64 ? ~0ull : n <= 0 ? 0ull : (1ull << n) - 1; }
+
 // query rows per block: the wide tile wherever its list fits (K <= 64) and there is more than one narrow tile of queries
 static inline int query_rows_per_block(int Q, int K) { return K <= 64 && Q > 64 ? 128 : 64; }
 
 // WQ: 32-row query tiles per wave (block = 64 WQ query rows x 128 gallery rows, waves 2 x 2); KL: list capacity (K <= KL).
-template <class OP, int WQ, int KL>
+// By item only (the plain kernels pass null / 0): g_item int32 [N], q_skip int32 [Q] or null, distinct, out_c.
+template <class OP, bool ITEMS, int WQ, int KL>
 __device__ __forceinline__ void search_block(const typename OP::elem* __restrict__ q, int64_t ld_q, const typename OP::elem* __restrict__ g, int64_t ld_g, int Q,
-                                             int N, int E, int K, int per, int S, int64_t idx_base, float* __restrict__ out_v, int64_t* __restrict__ out_i) {
+                                             int N, int E, int K, int per, int S, int64_t idx_base, const int32_t* __restrict__ g_item,
+                                             const int32_t* __restrict__ q_skip, int distinct, float* __restrict__ out_v, int64_t* __restrict__ out_i,
+                                             int32_t* __restrict__ out_c) {
     using elem = typename OP::elem;
     constexpr int LDT = OP::LDT;
     constexpr int BQ = 64 * WQ;
@@ -37,19 +56,28 @@ __device__ __forceinline__ void search_block(const typename OP::elem* __restrict
     constexpr int NQU = 2 * WQ, NGU = 4;                   // a thread's load units per stage: (row, group of 8) of the [BQ][64] and [128][64] stage images
     __shared__ __attribute__((aligned(16))) elem sQ[BQ * LDT];
     __shared__ __attribute__((aligned(16))) elem sG[BN * LDT];
-    __shared__ float lv[BQ * KL];      // sorted top list of every row, slots >= count hold (-inf, NO_J)
+    __shared__ float lv[BQ * KL];      // sorted top list of every row, slots >= count hold (-inf, NO_J); with `distinct` its item codes are all different
     __shared__ int lj[BQ * KL];
     __shared__ float cv[BQ * CB];      // candidate buffer, any order
     __shared__ int cj[BQ * CB];
     __shared__ int cnt[BQ];
+    int* skips = nullptr;              // by item: the row's skip code, -1: none
+    if constexpr (ITEMS) {
+        __shared__ int sk[BQ];         // (hipcc orders a kernel's LDS by the arrays' names: renaming one moves the others)
+        skips = sk;
+    }
 
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, r = lane & 31, h = lane >> 5;
     const int wq = wave >> 1, wg = wave & 1;
     const int q0 = blockIdx.x * BQ, s = blockIdx.y;
     const int jbeg = (int)min((int64_t)N, (int64_t)s * per), jend = (int)min((int64_t)N, (int64_t)jbeg + per);
+    const bool has_skip = ITEMS && q_skip != nullptr;
 
     for (int x = tid; x < BQ * KL; x += 256) { lv[x] = -INFINITY; lj[x] = NO_J; }
-    for (int x = tid; x < BQ; x += 256) cnt[x] = 0;
+    for (int x = tid; x < BQ; x += 256) {
+        cnt[x] = 0;
+        if constexpr (ITEMS) skips[x] = has_skip && q0 + x < Q ? q_skip[q0 + x] : -1;
+    }
     // (the first __syncthreads of the tile loop, or the one before the output, orders these writes)
 
     // fold the buffer of the rows that are full (or, at the end, non-empty) into their lists; wave w owns rows w, w + 4, ...
@@ -74,15 +102,65 @@ __device__ __forceinline__ void search_block(const typename OP::elem* __restrict
             const bool mine = lane < c;                      // buffer entry: rank = the list entries before it + the buffer entries before it
             const float mv = mine ? Cv[lane] : -INFINITY;
             const int mj = mine ? Cj[lane] : NO_J;
+            uint64_t bdom = 0, dm[NU];                       // by item: dominated buffer entries / list entries (bit = lane of chunk u)
+            if constexpr (ITEMS) {
+                // ---- dominance: an entry goes if another entry of list + buffer with its item code is before it.  The list's codes are all different, so
+                // only buffer entries can dominate a list entry; a buffer entry falls to a list entry or to another buffer entry.  An empty slot (-inf, NO_J,
+                // code -1) is before nothing, so it dominates nothing.
+#pragma unroll
+                for (int u = 0; u < NU; ++u) dm[u] = 0;
+                if (distinct) {
+                    int ec[NU];
+#pragma unroll
+                    for (int u = 0; u < NU; ++u) ec[u] = ej[u] != NO_J ? g_item[ej[u]] : -1;
+                    const int mc = mine ? g_item[mj] : -1;
+                    bool ld[NU];
+#pragma unroll
+                    for (int u = 0; u < NU; ++u) ld[u] = false;
+#pragma unroll
+                    for (int x = 0; x < CB; ++x) {
+                        const float xv = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(mv), x));
+                        const int xj = __builtin_amdgcn_readlane(mj, x);
+                        const int xc = __builtin_amdgcn_readlane(mc, x);
+                        bool d = mc == xc && before(mv, mj, xv, xj);             // this lane's buffer entry dominates x (strict order: never itself)
+#pragma unroll
+                        for (int u = 0; u < NU; ++u) {
+                            const bool same = ec[u] == xc;
+                            ld[u] |= same && before(xv, xj, ev[u], ej[u]);
+                            d |= same && before(ev[u], ej[u], xv, xj);
+                        }
+                        if (__ballot(d)) bdom |= 1ull << x;
+                    }
+#pragma unroll
+                    for (int u = 0; u < NU; ++u) dm[u] = __ballot(ld[u]);
+                }
+                // ---- ranks among the survivors: list entry p = the surviving list entries above it + the surviving buffer entries before it (below)
+#pragma unroll
+                for (int u = 0; u < NU; ++u) {
+                    int gone = __popcll(dm[u] & low_bits(lane));
+#pragma unroll
+                    for (int w = 0; w < u; ++w) gone += __popcll(dm[w]);
+                    if (rk[u] < KL) rk[u] -= gone;
+                    if ((dm[u] >> lane) & 1) rk[u] = KL;
+                }
+            }
             int lo = 0, hi = K;
             for (int step = 32 - __builtin_clz(K); step > 0; --step) {   // bit_length(K) halvings empty [0, K]
                 const int mid = (lo + hi) >> 1;
                 if (lo < hi) { if (before(Lv[mid], Lj[mid], mv, mj)) lo = mid + 1; else hi = mid; }
             }
             int mr = lo;
+            if constexpr (ITEMS) {                           // buffer entry: the surviving list entries before it = those before it minus the dominated ones
+#pragma unroll
+                for (int u = 0; u < NU; ++u) mr -= __popcll(dm[u] & low_bits(lo - 64 * u));
+                if ((bdom >> lane) & 1) mr = KL;
+            }
             // buffer entry x sits in lane x's registers: broadcast it from there (lanes >= c hold (-inf, NO_J), which is before nothing)
 #pragma unroll
             for (int x = 0; x < CB; ++x) {
+                if constexpr (ITEMS) {
+                    if ((bdom >> x) & 1) continue;           // wave-uniform
+                }
                 const float xv = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(mv), x));
                 const int xj = __builtin_amdgcn_readlane(mj, x);
 #pragma unroll
@@ -127,6 +205,16 @@ __device__ __forceinline__ void search_block(const typename OP::elem* __restrict
             for (int b = 0; b < 2; ++b)
 #pragma unroll
                 for (int x = 0; x < 16; ++x) acc[a][b][x] = 0.f;
+        int jc[2] = {-1, -1};                                // by item: item codes of this lane's two gallery rows, in flight during the multiply
+        if constexpr (ITEMS) {
+            if (has_skip) {
+#pragma unroll
+                for (int b = 0; b < 2; ++b) {
+                    const int j = jbeg + tile * BN + wg * 64 + b * 32 + r;
+                    if (j < jend) jc[b] = g_item[j];
+                }
+            }
+        }
         for (int chunk = 0; chunk < nchunk; ++chunk, ++it) {
             __syncthreads();
 #pragma unroll
@@ -146,10 +234,14 @@ __device__ __forceinline__ void search_block(const typename OP::elem* __restrict
                 const int i = wq * 32 * WQ + a * 32 + (x & 3) + 8 * (x >> 2) + 4 * h;
                 const float tv = lv[i * KL + K - 1];
                 const int tj = lj[i * KL + K - 1];
+                int skip = -1;
+                if constexpr (ITEMS) skip = skips[i];
 #pragma unroll
                 for (int b = 0; b < 2; ++b) {
                     const int j = jbeg + tile * BN + wg * 64 + b * 32 + r;
-                    if (j < jend && q0 + i < Q && before(acc[a][b][x], j, tv, tj)) pend |= 1ull << ((a * 2 + b) * 16 + x);
+                    bool eligible = true;                    // (a NaN score is before nothing)
+                    if constexpr (ITEMS) eligible = skip < 0 || jc[b] != skip;
+                    if (j < jend && q0 + i < Q && eligible && before(acc[a][b][x], j, tv, tj)) pend |= 1ull << ((a * 2 + b) * 16 + x);
                 }
             }
         while (__syncthreads_or(pend != 0)) {
@@ -200,7 +292,55 @@ __device__ __forceinline__ void search_block(const typename OP::elem* __restrict
         const int64_t o = ((int64_t)(q0 + i) * S + s) * K + p;
         out_v[o] = j == NO_J ? -INFINITY : lv[i * KL + p];
         out_i[o] = j == NO_J ? (int64_t)-1 : idx_base + j;
+        if constexpr (ITEMS) out_c[o] = j == NO_J ? -1 : g_item[j];
     }
+}
+
+// The host side of the four search entries: argument rules, split rule, workspace layout, launch, and the merge of the splits' partial lists.
+//   name             the entry's, for the messages
+//   e_mul / ld_mul   what E and the row strides must be multiples of in this operand format (fp32 rows: 4 / 4, bf16 rows: 16 / 8)
+//   kern             the entry's score kernel at (WQ, KL) = (2, 16) (2, 64) (1, 16) (1, 128): the wide tile where query_rows_per_block says so, the short
+//                    list for K <= 16
+// The plain entries (ITEMS == false) pass null g_item / q_skip / items and distinct = 0; nothing reads them.
+template <class OP, bool ITEMS, class KERN>
+int search_host(const char* name, int e_mul, int ld_mul, KERN* const (&kern)[4], const typename OP::elem* q, int64_t ld_q, const typename OP::elem* g,
+                int64_t ld_g, int Q, int64_t N, int E, int K, int n_split, int64_t idx_base, const int32_t* g_item, const int32_t* q_skip, int distinct, float* vals,
+                int64_t* idx, int32_t* items, void* workspace, void* stream) {
+    SC_CHECK_ARG(E >= e_mul && E <= 1024 && E % e_mul == 0, "%s: E=%d must be a multiple of %d in [%d, 1024]", name, E, e_mul, e_mul);
+    SC_CHECK_ARG(ld_q >= E && ld_g >= E && ld_q % ld_mul == 0 && ld_g % ld_mul == 0, "%s: ld_q=%lld / ld_g=%lld must be multiples of %d and >= E=%d", name,
+                 (long long)ld_q, (long long)ld_g, ld_mul, E);
+    SC_CHECK_ARG((((uintptr_t)q | (uintptr_t)g) & 15) == 0, "%s: q and g must be 16-byte aligned", name);
+    SC_CHECK_ARG(K >= 1 && K <= 128, "%s: K=%d must be in [1, 128]", name, K);
+    SC_CHECK_ARG(N < ((int64_t)1 << 31), "%s: N=%lld must be below 2^31", name, (long long)N);
+    SC_CHECK_ARG(K <= N, "%s: K=%d exceeds N=%lld", name, K, (long long)N);
+    SC_CHECK_ARG(n_split >= 0 && n_split <= 1024, "%s: n_split=%d must be in [0, 1024] (0 = auto)", name, n_split);
+    SC_CHECK_ARG(Q >= 0, "%s: Q=%d is negative", name, Q);
+    if (Q == 0) return 0;
+    SC_CHECK_ARG(q && g && vals && idx, "%s: null operand", name);
+    if constexpr (ITEMS) {
+        SC_CHECK_ARG(g_item, "%s: null g_item (an int32 item code per gallery row is required)", name);
+        SC_CHECK_ARG(items, "%s: null items", name);
+    }
+    const int S = n_split ? n_split : sc_search_splits(Q, N, K);
+    SC_CHECK_ARG(S == 1 || workspace, "%s: %d splits need a workspace (%s)", name, S, ITEMS ? "sc_search_items_workspace_bytes" : "sc_search_workspace_bytes");
+    const int per = (int)((N + S - 1) / S);
+    int64_t* wi = (int64_t*)workspace;                       // [Q][S][K] i64, then [Q][S][K] f32 and, by item, [Q][S][K] i32
+    float* wv = (float*)(wi + (int64_t)Q * S * K);
+    int32_t* wc = (int32_t*)(wv + (int64_t)Q * S * K);
+    float* ov = S == 1 ? vals : wv;
+    int64_t* oi = S == 1 ? idx : wi;
+    const int bq = query_rows_per_block(Q, K);
+    const dim3 grid((unsigned)((Q + bq - 1) / bq), (unsigned)S);
+    KERN* const k = kern[(bq == 128 ? 0 : 2) + (K <= 16 ? 0 : 1)];
+    if constexpr (ITEMS)
+        hipLaunchKernelGGL(k, grid, dim3(256), 0, (hipStream_t)stream, q, ld_q, g, ld_g, Q, (int)N, E, K, per, S, idx_base, g_item, q_skip, distinct, ov, oi,
+                           S == 1 ? items : wc);
+    else
+        hipLaunchKernelGGL(k, grid, dim3(256), 0, (hipStream_t)stream, q, ld_q, g, ld_g, Q, (int)N, E, K, per, S, idx_base, ov, oi);
+    SC_CHECK_LAUNCH();
+    if (S == 1) return 0;
+    if constexpr (ITEMS) return sc_topk_merge_items(wv, wi, wc, Q, S * K, K, distinct, vals, idx, items, stream);
+    else return sc_topk_merge(wv, wi, Q, S * K, K, vals, idx, stream);
 }
 
 }  // namespace search_core

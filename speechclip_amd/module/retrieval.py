@@ -127,33 +127,36 @@ class EmbeddingIndex:
         dev = self._device()
         if not 1 <= k <= min(128, max(self._n, 1)) or self._n == 0:
             raise ValueError(f"k={k} must be in [1, min(128, {self._n} stored rows)]")
-        if distinct or exclude is not None:
-            return self._search_items(queries, k, bool(distinct), exclude, dev)
+        distinct, by_item = bool(distinct), bool(distinct) or exclude is not None
+        codes, skip = self._item_arguments(queries, k, distinct, exclude) if by_item else ([None] * len(self.segments), None)
         q = self._rows(queries)
-        search_topk = ops.search_topk_bf16 if self.storage == "bf16" else ops.search_topk
-        parts_v, parts_i, base = [], [], 0
-        for seg in self.segments:
+        if skip is not None:
+            skip = torch.tensor(skip, dtype=torch.int32, device=dev)
+        bf16 = self.storage == "bf16"
+        search_topk, search_items = (ops.search_topk_bf16, ops.search_items_bf16) if bf16 else (ops.search_topk, ops.search_items)
+        parts, base = [], 0
+        for seg, code in zip(self.segments, codes):
             kk = min(k, seg.shape[0])
-            v, i = search_topk(q, seg, kk, idx_base=base)
+            part = search_items(q, seg, kk, code, q_skip=skip, distinct=distinct, idx_base=base) if by_item else search_topk(q, seg, kk, idx_base=base)
             if kk < k:                             # a segment shorter than k: its list is padded with entries that take no part in the merge
-                v = torch.cat([v, torch.full((q.shape[0], k - kk), float("-inf"), device=dev)], 1)
-                i = torch.cat([i, torch.full((q.shape[0], k - kk), -1, device=dev, dtype=torch.int64)], 1)
-            parts_v.append(v), parts_i.append(i)
+                part = [torch.cat([t, torch.full((q.shape[0], k - kk), fill, device=dev, dtype=t.dtype)], 1) for t, fill in zip(part, (float("-inf"), -1, -1))]
+            parts.append(part)
             base += seg.shape[0]
-        if len(parts_v) == 1:
-            scores, pos = parts_v[0], parts_i[0]
+        if len(parts) == 1:
+            scores, pos = parts[0][:2]
         else:
-            scores, pos = ops.topk_merge(torch.cat(parts_v, 1), torch.cat(parts_i, 1), k)
+            joined = [torch.cat(t, 1) for t in zip(*parts)]
+            scores, pos = (ops.topk_merge_items(*joined, k, distinct) if by_item else ops.topk_merge(*joined, k))[:2]
         return scores, pos, self._ids_of(pos)
 
     def _ids_of(self, pos: torch.Tensor) -> list:
         host = pos.cpu().tolist()
         return host if self.ids is None else [[self.ids[p] if p >= 0 else None for p in row] for row in host]
 
-    def _search_items(self, queries, k: int, distinct: bool, exclude, dev):
-        """search with distinct / exclude: every segment through sc_search_items[_bf16] with its item codes, partial lists joined by sc_topk_merge_items
-        (exact: a segment is a split).  The arguments are checked on the host before anything runs."""
-        from .. import ops
+    def _item_arguments(self, queries, k: int, distinct: bool, exclude):
+        """search with distinct / exclude -> (one tensor of item codes per segment, the queries' skip codes as a host list or None): every segment goes
+        through sc_search_items[_bf16] with its item codes, and the partial lists are joined by sc_topk_merge_items (exact: a segment is a split).  The
+        arguments are checked on the host before anything runs."""
         if exclude is not None:
             exclude = exclude.detach().cpu().tolist() if torch.is_tensor(exclude) else list(exclude)
             if len(exclude) != len(queries):
@@ -161,30 +164,11 @@ class EmbeddingIndex:
         codes, table, n_ids = self._item_codes()
         if distinct and k > min(128, n_ids):
             raise ValueError(f"k={k} must be in [1, min(128, {n_ids} different ids)] with distinct=True")
-        q = self._rows(queries)
-        skip = None
-        if exclude is not None:
-            if table is None:                      # no ids: the id of a row is its position
-                host = [x if isinstance(x, int) and 0 <= x < self._n else -1 for x in exclude]
-            else:
-                host = [-1 if x is None else table.get(x, -1) for x in exclude]
-            skip = torch.tensor(host, dtype=torch.int32, device=dev)
-        search_items = ops.search_items_bf16 if self.storage == "bf16" else ops.search_items
-        parts, base = [], 0
-        for seg, code in zip(self.segments, codes):
-            kk = min(k, seg.shape[0])
-            v, i, c = search_items(q, seg, kk, code, q_skip=skip, distinct=distinct, idx_base=base)
-            if kk < k:                             # a segment shorter than k: padded with entries that take no part in the merge
-                v = torch.cat([v, torch.full((q.shape[0], k - kk), float("-inf"), device=dev)], 1)
-                i = torch.cat([i, torch.full((q.shape[0], k - kk), -1, device=dev, dtype=torch.int64)], 1)
-                c = torch.cat([c, torch.full((q.shape[0], k - kk), -1, device=dev, dtype=torch.int32)], 1)
-            parts.append((v, i, c))
-            base += seg.shape[0]
-        if len(parts) == 1:
-            scores, pos, _ = parts[0]
-        else:
-            scores, pos, _ = ops.topk_merge_items(*(torch.cat(t, 1) for t in zip(*parts)), k, distinct)
-        return scores, pos, self._ids_of(pos)
+        if exclude is None:
+            return codes, None
+        if table is None:                          # no ids: the id of a row is its position
+            return codes, [x if isinstance(x, int) and 0 <= x < self._n else -1 for x in exclude]
+        return codes, [-1 if x is None else table.get(x, -1) for x in exclude]
 
     def astype(self, storage: str) -> "EmbeddingIndex":
         """A new index with the same segment boundaries and ids in the other storage: fp32 -> bf16 rounds the stored rows (to nearest even), bf16 -> fp32

@@ -1070,36 +1070,46 @@ def retrieval_ranks(score, own_ids, cand_ids):
     return rank
 
 
-# ---- gallery search (search.hip, search_bf16.hip) ----
-def _search_topk(entry, dtype, q, g, k, n_split, idx_base, workspace):
-    """The two storage formats of the fused search: the same shapes, outputs, split rule and workspace; `entry` and the rows' dtype differ."""
+# ---- gallery search (search.hip, search_bf16.hip, search_items.hip) ----
+def _search(entry, dtype, q, g, k, n_split, idx_base, workspace, by_item=None):
+    """The four entries of the fused search: the same shapes, split rule and (vals, idx) outputs; `entry` and the rows' dtype differ.  by_item = (g_item,
+    q_skip, distinct) selects by item (sc_search_items*): the item codes of the gallery rows, the queries' skip codes or None, and a third output."""
     _need_cuda(q, g)
     assert q.dtype == dtype and g.dtype == dtype and q.dim() == 2 and g.dim() == 2 and q.stride(1) == 1 and g.stride(1) == 1
     assert q.shape[1] == g.shape[1], (q.shape, g.shape)
     Q, E = q.shape
     N, k = g.shape[0], int(k)
-    vals = torch.empty(Q, k, device=q.device, dtype=torch.float32)
-    idx = torch.empty(Q, k, device=q.device, dtype=torch.int64)
-    nbytes = lib().sc_search_workspace_bytes(Q, N, k, int(n_split))
+    out = [torch.empty(Q, k, device=q.device, dtype=torch.float32), torch.empty(Q, k, device=q.device, dtype=torch.int64)]
+    extra, workspace_bytes = (), lib().sc_search_workspace_bytes
+    if by_item is not None:
+        g_item, q_skip, distinct = by_item
+        _need_cuda(g_item)
+        assert g_item.dtype == torch.int32 and g_item.shape == (N,) and g_item.is_contiguous(), (g_item.dtype, g_item.shape)
+        if q_skip is not None:
+            _need_cuda(q_skip)
+            assert q_skip.dtype == torch.int32 and q_skip.shape == (Q,) and q_skip.is_contiguous(), (q_skip.dtype, q_skip.shape)
+        out.append(torch.empty(Q, k, device=q.device, dtype=torch.int32))
+        extra, workspace_bytes = (ptr(g_item), ptr(q_skip), int(bool(distinct))), lib().sc_search_items_workspace_bytes
+    nbytes = workspace_bytes(Q, N, k, int(n_split))
     if workspace is None and nbytes > 0:
         workspace = torch.empty(nbytes, device=q.device, dtype=torch.uint8)
     assert workspace is None or (workspace.is_cuda and workspace.numel() * workspace.element_size() >= nbytes)
-    check(getattr(lib(), entry)(ptr(q), q.stride(0), ptr(g), g.stride(0), Q, N, E, k, int(n_split), int(idx_base), ptr(vals), ptr(idx), ptr(workspace),
+    check(getattr(lib(), entry)(ptr(q), q.stride(0), ptr(g), g.stride(0), Q, N, E, k, int(n_split), int(idx_base), *extra, *(ptr(t) for t in out), ptr(workspace),
                                 stream()), entry)
-    return vals, idx
+    return tuple(out)
 
 
 def search_topk(q, g, k, n_split=0, idx_base=0, workspace=None):
     """q f32 [Q, E], g f32 [N, E] (device, last stride 1) -> (vals f32 [Q, k], idx i64 [Q, k]): for every query the k gallery rows with the largest
     fp32 fmaf-chain score, ordered by (score descending, row ascending); idx = idx_base + row.  No [Q, N] score image is formed (sc_search_topk).
     n_split = 0: the library's rule.  `workspace`: a caller's uint8 buffer of at least sc_search_workspace_bytes (tests guard it); default: allocated here."""
-    return _search_topk("sc_search_topk", torch.float32, q, g, k, n_split, idx_base, workspace)
+    return _search("sc_search_topk", torch.float32, q, g, k, n_split, idx_base, workspace)
 
 
 def search_topk_bf16(q, g, k, n_split=0, idx_base=0, workspace=None):
     """search_topk on bf16 rows (search_bf16.hip): q bf16 [Q, E], g bf16 [N, E] (device, last stride 1, E % 16 == 0) -> (vals f32 [Q, k], idx i64 [Q, k]).
     The bf16 products are exact and summed in fp32 on the bf16 MFMA (sc_search_topk_bf16's contract); order, splits and workspace as search_topk."""
-    return _search_topk("sc_search_topk_bf16", bf16, q, g, k, n_split, idx_base, workspace)
+    return _search("sc_search_topk_bf16", bf16, q, g, k, n_split, idx_base, workspace)
 
 
 def topk_merge(vals, idx, k):
@@ -1115,41 +1125,17 @@ def topk_merge(vals, idx, k):
     return out_v, out_i
 
 
-# ---- gallery search by item (search_items.hip) ----
-def _search_items(entry, dtype, q, g, k, g_item, q_skip, distinct, n_split, idx_base, workspace):
-    """The two storage formats of the id-aware search: _search_topk plus the item codes of the gallery rows, the queries' skip codes and the third output."""
-    _need_cuda(q, g, g_item)
-    assert q.dtype == dtype and g.dtype == dtype and q.dim() == 2 and g.dim() == 2 and q.stride(1) == 1 and g.stride(1) == 1
-    assert q.shape[1] == g.shape[1], (q.shape, g.shape)
-    Q, E = q.shape
-    N, k = g.shape[0], int(k)
-    assert g_item.dtype == torch.int32 and g_item.shape == (N,) and g_item.is_contiguous(), (g_item.dtype, g_item.shape)
-    if q_skip is not None:
-        _need_cuda(q_skip)
-        assert q_skip.dtype == torch.int32 and q_skip.shape == (Q,) and q_skip.is_contiguous(), (q_skip.dtype, q_skip.shape)
-    vals = torch.empty(Q, k, device=q.device, dtype=torch.float32)
-    idx = torch.empty(Q, k, device=q.device, dtype=torch.int64)
-    items = torch.empty(Q, k, device=q.device, dtype=torch.int32)
-    nbytes = lib().sc_search_items_workspace_bytes(Q, N, k, int(n_split))
-    if workspace is None and nbytes > 0:
-        workspace = torch.empty(nbytes, device=q.device, dtype=torch.uint8)
-    assert workspace is None or (workspace.is_cuda and workspace.numel() * workspace.element_size() >= nbytes)
-    check(getattr(lib(), entry)(ptr(q), q.stride(0), ptr(g), g.stride(0), Q, N, E, k, int(n_split), int(idx_base), ptr(g_item), ptr(q_skip), int(bool(distinct)),
-                                ptr(vals), ptr(idx), ptr(items), ptr(workspace), stream()), entry)
-    return vals, idx, items
-
-
 def search_items(q, g, k, g_item, q_skip=None, distinct=False, n_split=0, idx_base=0, workspace=None):
     """search_topk by item: g_item i32 [N] gives every gallery row an item code (>= 0), q_skip i32 [Q] (or None) names the item each query leaves out (< 0:
     none) -> (vals f32 [Q, k], idx i64 [Q, k], items i32 [Q, k]).  distinct=False: the first k rows whose item is not the query's skip code; distinct=True:
     the first k ITEMS, each by its best row.  Scores, order, splits and idx_base are search_topk's; missing slots hold -inf / -1 / -1 (sc_search_items).
     `workspace`: a caller's uint8 buffer of at least sc_search_items_workspace_bytes; default: allocated here."""
-    return _search_items("sc_search_items", torch.float32, q, g, k, g_item, q_skip, distinct, n_split, idx_base, workspace)
+    return _search("sc_search_items", torch.float32, q, g, k, n_split, idx_base, workspace, (g_item, q_skip, distinct))
 
 
 def search_items_bf16(q, g, k, g_item, q_skip=None, distinct=False, n_split=0, idx_base=0, workspace=None):
     """search_items on bf16 rows: search_topk_bf16's scores under the same selection (sc_search_items_bf16)."""
-    return _search_items("sc_search_items_bf16", bf16, q, g, k, g_item, q_skip, distinct, n_split, idx_base, workspace)
+    return _search("sc_search_items_bf16", bf16, q, g, k, n_split, idx_base, workspace, (g_item, q_skip, distinct))
 
 
 def topk_merge_items(vals, idx, items, k, distinct):
