@@ -765,6 +765,30 @@ int sc_search_items_bf16(const void* q, int64_t ld_q, const void* g, int64_t ld_
                          const int32_t* g_item, const int32_t* q_skip, int distinct, float* vals, int64_t* idx, int32_t* items, void* workspace, void* stream);
 int sc_topk_merge_items(const float* vals_in, const int64_t* idx_in, const int32_t* items_in, int Q, int L, int K, int distinct, float* vals, int64_t* idx,
                         int32_t* items, void* stream);
+
+/* ---- Gallery search, fp32 re-score of a shortlist: the second stage of a two-stage search (csrc/search_rescore.hip).  A bf16 search (sc_search_topk_bf16 /
+ * sc_search_items_bf16 on the rounded rows) shortlists R >= K rows per query; this entry scores those rows on the fp32 rows, returns the first K of them and
+ * says per query whether an error bound given by the caller PROVES that the first K of the shortlist are the first K of the whole gallery.
+ * q f32 [Q, E] / g f32 [N, E] with row strides ld_q / ld_g (elements); cand_idx i64 [Q, R]: the shortlist as the first stage wrote it (idx_base + j, or -1
+ * for an empty slot); short_vals f32 [Q, R]: that stage's scores, descending; eps f32 [Q].  RESCORE CONTRACT (restated on the host, with the derivation of
+ * eps, in tests/search_rerank_ref.py):
+ *   score      for every slot with cand_idx != -1 and 0 <= cand_idx - idx_base < N, j = cand_idx - idx_base and s(i, j) = the fp32 chain of sc_search_topk:
+ *              acc = +0.0f; for e ascending: acc = fmaf(q[i*ld_q + e], g[j*ld_g + e], acc) -- one accumulator, never split or reordered, subnormals kept:
+ *              the bits of sc_search_topk's score of the same pair.  Any other slot is never dereferenced and takes no part.
+ *   order      score descending, then j ascending; a NaN score takes no part.
+ *   result     vals f32 [Q, K] / idx i64 [Q, K] (= idx_base + j): the first K slots of row i in that order; missing slots hold -inf / -1.  The slots of one
+ *              row are expected to name distinct rows.
+ *   certified  int32 [Q]: certified[i] = 1 iff all R slots of row i name a row in range, short_vals[i, R-1] is not NaN, and either R == N or
+ *              (double)vals[i, K-1] > (double)short_vals[i, R-1] + (double)eps[i] (strict, in fp64); else 0.  What it proves: if every first-stage score is
+ *              within eps[i] of the fp32 chain of the same pair, a row outside the shortlist has a first-stage score <= short_vals[i, R-1], hence a chain
+ *              score <= short_vals[i, R-1] + eps[i] < vals[i, K-1]: it comes after the K returned rows, ties included.
+ *   pure       row i of vals / idx / certified depends on row i of q, cand_idx, short_vals and eps, on g, K, R, N and idx_base only: not on i's position in
+ *              the call and not on the other queries.  No atomics; every output element is written once.
+ *   reads      rows [0, Q) of q, cand_idx, short_vals and eps; E elements of the rows of g that an in-range slot names; nothing else.
+ *   refused    (nonzero rc + sc_last_error, nothing launched) E % 4 != 0 or E outside [4, 1024]; ld_q / ld_g < E or not multiples of 4; q or g not 16-byte
+ *              aligned; K outside [1, 128]; R outside [K, 128]; N outside [1, 2^31); Q < 0; a null operand.  Q == 0 returns 0 and launches nothing. */
+int sc_search_rescore(const float* q, int64_t ld_q, const float* g, int64_t ld_g, int Q, int64_t N, int E, const int64_t* cand_idx, const float* short_vals,
+                      int R, const float* eps, int K, int64_t idx_base, float* vals, int64_t* idx, int32_t* certified, void* stream);
 #ifdef __cplusplus
 }
 #endif

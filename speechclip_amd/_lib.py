@@ -189,6 +189,7 @@ def _declare(L):
         "sc_search_items": ([P, L64, P, L64, I, L64, I, I, I, L64, P, P, I, P, P, P, P, P], c_int),
         "sc_search_items_bf16": ([P, L64, P, L64, I, L64, I, I, I, L64, P, P, I, P, P, P, P, P], c_int),
         "sc_topk_merge_items": ([P, P, P, I, I, I, I, P, P, P, P], c_int),
+        "sc_search_rescore": ([P, L64, P, L64, I, L64, I, P, P, I, P, I, L64, P, P, P, P], c_int),
     }
     for name, (args, res) in sigs.items():
         fn = getattr(L, name)   # AttributeError here = header/library mismatch: fail loudly

@@ -124,10 +124,11 @@ class KWClipBase(BaseLightningModel):
         finally:
             self.train(was_training)
 
-    def build_index(self, images=None, sents=None, wav=None, ids=None, batch_size: int = 256, storage: str = "fp32") -> EmbeddingIndex:
+    def build_index(self, images=None, sents=None, wav=None, ids=None, batch_size: int = 256, storage: str = "fp32", shadow: bool = False) -> EmbeddingIndex:
         """An EmbeddingIndex over the items of ONE modality (images: paths / decoded frames / a [n, 3, H, W] tensor; sents: sentences / token ids; wav: whatever
         encode_speech takes).  Every batch of `batch_size` items is encoded and added as one segment; `ids` (int64 tensor or hashables such as paths)
-        label the items, default: their positions.  storage: "fp32" or "bf16" rows (EmbeddingIndex)."""
+        label the items, default: their positions.  storage: "fp32" or "bf16" rows; shadow=True: fp32 rows with their bf16 shadow, for search(..., rerank=R)
+        (EmbeddingIndex)."""
         items = next(x for x in (images, sents, wav, ()) if x is not None)
         n = len(items)
         if ids is not None and len(ids) != n:
@@ -137,17 +138,17 @@ class KWClipBase(BaseLightningModel):
             part = items[at:at + batch_size]
             feat = self._embed(images=part if images is not None else None, sents=part if sents is not None else None, wav=part if wav is not None else None)
             if index is None:
-                index = EmbeddingIndex(feat.shape[1], device=feat.device, storage=storage)
+                index = EmbeddingIndex(feat.shape[1], device=feat.device, storage=storage, shadow=shadow)
             index.add(feat, None if ids is None else ids[at:at + batch_size])
         if index is None:
             raise ValueError("give exactly one of images, sents, wav, with at least one item")
         return index
 
-    def search(self, index: EmbeddingIndex, k: int, images=None, sents=None, wav=None, distinct: bool = False, exclude=None):
+    def search(self, index: EmbeddingIndex, k: int, images=None, sents=None, wav=None, distinct: bool = False, exclude=None, rerank=None):
         """The k nearest items of `index` for every query of one modality -> (scores f32 [Q, k], positions i64 [Q, k], ids): EmbeddingIndex.search.
         distinct=True: the k nearest different ids (an index of several captions per image answers with images); exclude: one id per query to leave out
-        (hard negatives: the nearest items that are not the query's own)."""
-        return index.search(self._embed(images=images, sents=sents, wav=wav), k, distinct=distinct, exclude=exclude)
+        (hard negatives: the nearest items that are not the query's own); rerank=R: the same result by the two-stage search of an index with a shadow."""
+        return index.search(self._embed(images=images, sents=sents, wav=wav), k, distinct=distinct, exclude=exclude, rerank=rerank)
 
     def forward(self, batch: dict) -> tuple:
         raise NotImplementedError()

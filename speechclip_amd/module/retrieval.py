@@ -39,6 +39,19 @@ def mutualRetrieval(score_per_A: torch.Tensor, score_per_B: torch.Tensor, AB_ans
     return ab, ba, mean
 
 
+RERANK_MERGE_CANDIDATES = 8192         # most candidates per query that the first stage of the two-stage search hands to sc_topk_merge (splits x R)
+RERANK_INFLATE = 1.0 + 2.0 ** -22     # covers the fp64 roundings of the norms and of eps, and its rounding to fp32 (2^-24), with room to spare
+
+
+def rerank_kappa(E: int) -> float:
+    """kappa(E) of the two-stage search: |bf16-stage score of the rounded rows - fp32 chain of the stored rows| <= kappa(E) ||q|| ||g|| for finite, normal
+    operands.  Three terms (statement and derivation: tests/search_rerank_ref.py): rounding both operands to bf16 (8 significand bits, unit roundoff 2^-8:
+    2^-7 + 2^-16), the bf16 entry's accumulation bound c 2^-24 with c = 2E / (1 - 2E 2^-24) carried from the rounded rows back to the stored ones by
+    (1 + 2^-8)^2, and gamma_E = E 2^-24 / (1 - E 2^-24) of the fp32 fmaf chain."""
+    u = 2.0 ** -24
+    return (2.0 ** -7 + 2.0 ** -16) + 2.0 * E * u / (1.0 - 2.0 * E * u) * (1.0 + 2.0 ** -8) ** 2 + E * u / (1.0 - E * u)
+
+
 class EmbeddingIndex:
     """A gallery of embeddings on the device and the answer to "which k stored items are nearest to this query?" (sc_search_topk: fused fp32
     similarity + top-k, no [Q, N] score image).  Rows are kept as fp32 SEGMENTS, one per `add`; adding never reallocates earlier segments.  A search runs
@@ -47,16 +60,23 @@ class EmbeddingIndex:
     storage="bf16" (dim % 16 == 0) keeps the rows in bf16 instead: rows and queries are normalised in fp32 as before and then rounded to bf16 (round to
     nearest even), and sc_search_topk_bf16 forms the scores -- exact bf16 products summed in fp32, returned as fp32; half the bytes per row, the same
     segments, positions, ids and merge, and the same one-segment equality.  The default stays fp32.
+    shadow=True (fp32 storage, dim % 16 == 0) keeps, beside every fp32 segment, the same rows rounded to bf16 -- exactly what astype("bf16") holds -- and the
+    running maximum of the stored rows' norms: what search(..., rerank=R) needs to answer with the fp32 result at close to the bf16 search's cost.
     There is no host implementation: without the library's GPU `add` / `search` raise SpeechClipHipError, like mutualRetrieval."""
 
     STORAGES = {"fp32": torch.float32, "bf16": torch.bfloat16}
     STORAGE_BITS = {"fp32": 32, "bf16": 16}            # how state_dict names the storage
 
-    def __init__(self, dim: int, device=None, normalize: bool = True, storage: str = "fp32"):
+    def __init__(self, dim: int, device=None, normalize: bool = True, storage: str = "fp32", shadow: bool = False):
         if storage not in self.STORAGES:
             raise ValueError(f"storage={storage!r} must be one of {sorted(self.STORAGES)}")
         if storage == "bf16" and int(dim) % 16 != 0:
             raise ValueError(f"storage='bf16' needs dim % 16 == 0 (sc_search_topk_bf16), got dim={dim}")
+        if shadow and (storage != "fp32" or int(dim) % 16 != 0):
+            raise ValueError(f"shadow=True needs storage='fp32' and dim % 16 == 0 (sc_search_topk_bf16 on the shadow rows), got storage={storage!r}, dim={dim}")
+        self.shadow = bool(shadow)
+        self.shadow_segments: List[torch.Tensor] = []  # with a shadow: segment s rounded to bf16
+        self._norm_max = None                      # with a shadow: fp64 device scalar, the largest stored row norm so far
         self.dim, self.normalize, self.storage = int(dim), bool(normalize), storage
         self.device = torch.device(device) if device is not None else None
         self.segments: List[torch.Tensor] = []
@@ -101,8 +121,25 @@ class EmbeddingIndex:
         if n:
             self.segments.append(rows)
             self._n += n
+            if self.shadow:
+                self._add_shadow(rows)
         self._codes = None
         return self
+
+    def _add_shadow(self, rows: torch.Tensor) -> None:
+        self.shadow_segments.append(rows.to(torch.bfloat16))             # round to nearest even, after the fp32 normalisation
+        top = torch.stack([rows[at:at + 65536].double().norm(dim=1).max() for at in range(0, rows.shape[0], 65536)]).max()   # fp64, in bounded pieces
+        self._norm_max = top if self._norm_max is None else torch.maximum(self._norm_max, top)
+
+    def with_shadow(self) -> "EmbeddingIndex":
+        """A new fp32 index over the same segments (shared, they are never written) and ids, with shadow rows: what search(..., rerank=R) needs."""
+        out = EmbeddingIndex(self.dim, device=self.device, normalize=self.normalize, storage=self.storage, shadow=True)
+        out.segments = list(self.segments)
+        out.ids = None if self.ids is None else list(self.ids)
+        out._n = self._n
+        for seg in out.segments:
+            out._add_shadow(seg)
+        return out
 
     def _item_codes(self):
         """-> (one int32 device tensor of item codes per segment, {id: code} or None, number of codes).  Equal ids share a code, assigned in first-seen
@@ -117,21 +154,44 @@ class EmbeddingIndex:
             self._codes = (segs, table, self._n if table is None else len(table))
         return self._codes
 
-    def search(self, queries: torch.Tensor, k: int, distinct: bool = False, exclude: Optional[Sequence[Hashable]] = None):
+    def search(self, queries: torch.Tensor, k: int, distinct: bool = False, exclude: Optional[Sequence[Hashable]] = None, rerank: Optional[int] = None,
+               return_certified: bool = False):
         """-> (scores f32 [Q, k] descending, positions i64 [Q, k], ids): ids[i][r] is the stored id of positions[i, r] (the position itself without ids).
         distinct=True: the k nearest DIFFERENT ids, each by its best row (rows that share an id are one item; k <= the number of different ids).
         exclude: one id per query (a sequence of len(queries)); rows carrying it are left out of that query's result -- None, or an id the index does not
-        hold, leaves out nothing.  With both defaults this is the plain search (sc_search_topk); otherwise sc_search_items, same scores and order."""
+        hold, leaves out nothing.  With both defaults this is the plain search (sc_search_topk); otherwise sc_search_items, same scores and order.
+        rerank=R (an index with a shadow, k <= R <= 128, distinct=False): the SAME result, bit for bit, by two stages -- a bf16 search of the shadow rows
+        shortlists R rows per query and segment, sc_search_rescore scores them on the fp32 rows and certifies the queries whose shortlist provably holds
+        the first k (rerank_kappa), and only the other queries go through the fp32 search.  return_certified=True (with rerank) appends a bool [Q] host
+        tensor: which queries the certificate covered."""
         from .. import ops
         k = int(k)
+        if rerank is not None:                     # the rules of the two-stage search are host rules: checked before anything touches the device
+            if not self.shadow:
+                raise ValueError("rerank needs an index with shadow rows: EmbeddingIndex(..., shadow=True) or index.with_shadow()")
+            if distinct:
+                raise ValueError("rerank with distinct=True is not supported: an item's best bf16 row need not be its best fp32 row")
+            if not k <= int(rerank) <= 128:
+                raise ValueError(f"rerank={rerank} must be in [k={k}, 128]")
+        elif return_certified:
+            raise ValueError("return_certified=True needs rerank=R: only the two-stage search certifies anything")
         dev = self._device()
         if not 1 <= k <= min(128, max(self._n, 1)) or self._n == 0:
             raise ValueError(f"k={k} must be in [1, min(128, {self._n} stored rows)]")
+        if rerank is not None:
+            return self._search_rerank(queries, k, int(rerank), bool(distinct), exclude, bool(return_certified))
         distinct, by_item = bool(distinct), bool(distinct) or exclude is not None
         codes, skip = self._item_arguments(queries, k, distinct, exclude) if by_item else ([None] * len(self.segments), None)
         q = self._rows(queries)
         if skip is not None:
             skip = torch.tensor(skip, dtype=torch.int32, device=dev)
+        scores, pos = self._search_prepared(q, k, distinct, by_item, codes, skip)
+        return scores, pos, self._ids_of(pos)
+
+    def _search_prepared(self, q: torch.Tensor, k: int, distinct: bool, by_item: bool, codes, skip):
+        """The one-stage search of prepared query rows (already normalised and in the storage type) -> (scores, positions)."""
+        from .. import ops
+        dev = q.device
         bf16 = self.storage == "bf16"
         search_topk, search_items = (ops.search_topk_bf16, ops.search_items_bf16) if bf16 else (ops.search_topk, ops.search_items)
         parts, base = [], 0
@@ -147,7 +207,47 @@ class EmbeddingIndex:
         else:
             joined = [torch.cat(t, 1) for t in zip(*parts)]
             scores, pos = (ops.topk_merge_items(*joined, k, distinct) if by_item else ops.topk_merge(*joined, k))[:2]
-        return scores, pos, self._ids_of(pos)
+        return scores, pos
+
+    def _search_rerank(self, queries, k: int, R: int, distinct: bool, exclude, return_certified: bool):
+        """search(..., rerank=R).  Per segment: stage 1 on the shadow rows with K = min(R, rows) (sc_search_topk_bf16, or sc_search_items_bf16 with the skip
+        codes), sc_search_rescore on the fp32 rows, the usual padding; then sc_topk_merge (a segment is a split: exact per-segment lists merge exactly).
+        A query is certified iff it is certified in every segment; the flags are read once, and the queries without the proof -- only those -- are run
+        through the one-stage fp32 search, whose rows do not depend on the other queries of the call (the entries' purity contract)."""
+        from .. import ops
+        by_item = exclude is not None
+        codes, skip_host = self._item_arguments(queries, k, False, exclude) if by_item else ([None] * len(self.segments), None)
+        q = self._rows(queries)
+        dev, Q = q.device, q.shape[0]
+        skip = None if skip_host is None else torch.tensor(skip_host, dtype=torch.int32, device=dev)
+        qb = q.to(torch.bfloat16)
+        # eps_i = kappa(E) ||q_i|| G in fp64, inflated once for the roundings of the norms, of this product and of its conversion to fp32
+        eps = (q.double().norm(dim=1) * self._norm_max.to(dev) * (rerank_kappa(self.dim) * RERANK_INFLATE)).to(torch.float32)
+        parts, base, flags = [], 0, None
+        for seg, sh, code in zip(self.segments, self.shadow_segments, codes):
+            rr = min(R, seg.shape[0])
+            kk = min(k, rr)
+            # sc_topk_merge takes K rounds over S K candidates per query: with K = R the automatic split count (chosen for K = 10-like lists) makes the
+            # merge, not the scan, the cost of a few queries against a large gallery -- the splits are capped so that a query merges at most 8192 candidates
+            S = max(1, min(ops.lib().sc_search_splits(Q, seg.shape[0], rr), RERANK_MERGE_CANDIDATES // rr))
+            short = (ops.search_items_bf16(qb, sh, rr, code, q_skip=skip, distinct=False, n_split=S, idx_base=base) if by_item else
+                     ops.search_topk_bf16(qb, sh, rr, n_split=S, idx_base=base))
+            v, i, c = ops.search_rescore(q, seg, short[1], short[0], eps, kk, idx_base=base)
+            if kk < k:
+                v, i = (torch.cat([t, torch.full((Q, k - kk), fill, device=dev, dtype=t.dtype)], 1) for t, fill in zip((v, i), (float("-inf"), -1)))
+            parts.append((v, i))
+            flags = c if flags is None else flags & c
+            base += seg.shape[0]
+        scores, pos = parts[0] if len(parts) == 1 else ops.topk_merge(*(torch.cat(t, 1) for t in zip(*parts)), k)
+        certified = flags.cpu().bool()                                   # the one read of the flags
+        redo = torch.nonzero(~certified).flatten()
+        if redo.numel():
+            rows = redo.to(dev)
+            sub_skip = None if skip is None else skip[rows].contiguous()
+            s2, p2 = self._search_prepared(q[rows].contiguous(), k, False, by_item, codes, sub_skip)
+            scores, pos = scores.index_copy(0, rows, s2), pos.index_copy(0, rows, p2)
+        out = (scores, pos, self._ids_of(pos))
+        return out + (certified,) if return_certified else out
 
     def _ids_of(self, pos: torch.Tensor) -> list:
         host = pos.cpu().tolist()
@@ -181,24 +281,29 @@ class EmbeddingIndex:
 
     def state_dict(self) -> dict:
         """Plain host values only (numbers, lists, None, host tensors).  "feats" holds the rows in their storage type (a bf16 tensor for a bf16 index: half
-        the file); "storage" names it by its width in bits, 32 or 16."""
+        the file); "storage" names it by its width in bits, 32 or 16; "shadow": True is there only for an index with shadow rows."""
         feats = torch.cat(self.segments, 0).cpu() if self.segments else torch.zeros(0, self.dim, dtype=self.STORAGES[self.storage])
-        return {"dim": self.dim, "normalize": self.normalize, "storage": self.STORAGE_BITS[self.storage], "feats": feats, "segment_rows": [s.shape[0] for s in self.segments],
-                "ids": None if self.ids is None else list(self.ids)}
+        sd = {"dim": self.dim, "normalize": self.normalize, "storage": self.STORAGE_BITS[self.storage], "feats": feats, "segment_rows": [s.shape[0] for s in self.segments],
+              "ids": None if self.ids is None else list(self.ids)}
+        if self.shadow:
+            sd["shadow"] = True                    # the shadow rows are not written: from_state_dict rounds them again
+        return sd
 
     @classmethod
     def from_state_dict(cls, sd: dict, device=None) -> "EmbeddingIndex":
         """Rebuilds the same segments from the stored rows (already normalised when the index normalises: they are not normalised again).  A dict without
-        a "storage" key was written before bf16 storage existed: fp32."""
+        a "storage" key was written before bf16 storage existed: fp32; one without a "shadow" key has none."""
         bits = sd.get("storage", 32)
         names = {b: name for name, b in cls.STORAGE_BITS.items()}
         if bits not in names:
             raise ValueError(f"state dict storage={bits!r} must be one of {sorted(names)} (bits per element)")
-        index = cls(sd["dim"], device=device, normalize=sd["normalize"], storage=names[bits])
+        index = cls(sd["dim"], device=device, normalize=sd["normalize"], storage=names[bits], shadow=bool(sd.get("shadow", False)))
         dev = index._device()
         at = 0
         for n in sd["segment_rows"]:
             index.segments.append(sd["feats"][at:at + n].to(dev, cls.STORAGES[index.storage]).contiguous())
+            if index.shadow:
+                index._add_shadow(index.segments[-1])
             at += n
         index._n = at
         index.ids = None if sd["ids"] is None else list(sd["ids"])

@@ -1154,6 +1154,28 @@ def topk_merge_items(vals, idx, items, k, distinct):
     return out_v, out_i, out_c
 
 
+def search_rescore(q, g, cand_idx, short_vals, eps, k, idx_base=0):
+    """The second stage of a two-stage search (search_rescore.hip): q f32 [Q, E], g f32 [N, E] (device, last stride 1), cand_idx i64 [Q, R] / short_vals f32
+    [Q, R] = a bf16 search's shortlist of the rounded rows (idx_base + row or -1; scores descending), eps f32 [Q] -> (vals f32 [Q, k], idx i64 [Q, k],
+    certified i32 [Q]): the first k shortlisted rows by search_topk's own fp32 score and order, and whether eps proves that no row outside the shortlist
+    belongs among them (sc_search_rescore)."""
+    _need_cuda(q, g, cand_idx, short_vals, eps)
+    assert q.dtype == torch.float32 and g.dtype == torch.float32 and q.dim() == 2 and g.dim() == 2 and q.stride(1) == 1 and g.stride(1) == 1
+    assert q.shape[1] == g.shape[1], (q.shape, g.shape)
+    Q, E = q.shape
+    N, k = g.shape[0], int(k)
+    assert cand_idx.dtype == torch.int64 and short_vals.dtype == torch.float32 and cand_idx.dim() == 2 and cand_idx.shape == short_vals.shape
+    assert cand_idx.shape[0] == Q and cand_idx.is_contiguous() and short_vals.is_contiguous(), (cand_idx.shape, short_vals.shape)
+    assert eps.dtype == torch.float32 and eps.shape == (Q,) and eps.is_contiguous(), (eps.dtype, eps.shape)
+    R = cand_idx.shape[1]
+    vals = torch.empty(Q, k, device=q.device, dtype=torch.float32)
+    idx = torch.empty(Q, k, device=q.device, dtype=torch.int64)
+    certified = torch.empty(Q, device=q.device, dtype=torch.int32)
+    check(lib().sc_search_rescore(ptr(q), q.stride(0), ptr(g), g.stride(0), Q, N, E, ptr(cand_idx), ptr(short_vals), R, ptr(eps), k, int(idx_base), ptr(vals),
+                                  ptr(idx), ptr(certified), stream()), "sc_search_rescore")
+    return vals, idx, certified
+
+
 # ---- cascaded tail, training (train_cascaded.hip) ----
 def attn_small_bwd(qkv16, dout, B, L, H, causal=True):
     """qkv bf16 [B*L, 3*H*64] (saved by the forward), dout f32 [B*L, H*64] -> dqkv f32 [B*L, 3*H*64]."""
