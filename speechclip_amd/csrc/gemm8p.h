@@ -27,3 +27,6 @@ struct Gemm8pParams {
 
 // gemm8p.hip.  0: launched; 1: shape outside the kernel's rules (nothing launched; the caller runs gemm256_kernel / gemm_bf16_kernel); < 0: error
 int sc_gemm8p_try(const Gemm8pParams& p, hipStream_t s);
+
+// gemm.hip.  Compute units of the current device, asked for once per process: the grid of every persistent GEMM kernel is one block per CU.
+int sc_gemm_num_cus();

@@ -834,8 +834,7 @@ int sc_gemm8p_try(const Gemm8pParams& pin, hipStream_t s) {
     const int grid = (int)tiles;
     const bool res = p.residual != nullptr;
     if (p.esteps != 1 && p.N <= 8192) {       // persistent form (esteps == 1: the plain per-tile kernel, A/B)
-        static int n_cu = 0;
-        if (!n_cu) { int dev = 0; (void)hipGetDevice(&dev); hipDeviceProp_t pr; (void)hipGetDeviceProperties(&pr, dev); n_cu = pr.multiProcessorCount > 0 ? pr.multiProcessorCount : 256; }
+        const int n_cu = sc_gemm_num_cus();
         const int pg = grid < n_cu ? grid : n_cu;
         // dynamic tile order: a slot of the counter ring per launch (SCHED_RING launches would have to be in flight at once for two to meet).  A launch
         // that is being CAPTURED into a HIP graph keeps the static order: its slot would be frozen into the graph node, and a replay could then run

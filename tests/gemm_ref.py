@@ -26,8 +26,8 @@ The bound of a real case, per element (U = 2^-24, TR = 2^-22, BF_STORE, H16_STOR
                     accumulator updates, (K / 32) u_acc |bias| on top.
     bias, residual  one U |result| each
     activation      the pre-activation's error through |gelu'| <= GELU_LIP (1.13; QuickGELU's largest slope is 1.10), plus the form's own constant:
-                      gelu_erf          GELU_ERF_FIT + (2 TR + 8 U) |want|        the 16-bit bf16 outputs of gemm_bf16_kernel          (gemm.hip:180)
-                      gelu_erf_precise  GELU_PRECISE (1 + |u|)                     its fp32 and IEEE-half outputs                       (gemm.hip:180)
+                      gelu_erf          GELU_ERF_FIT + (2 TR + 8 U) |want|        the 16-bit bf16 outputs of gemm_bf16_kernel          (its epilogue)
+                      gelu_erf_precise  GELU_PRECISE (1 + |u|)                     its fp32 and IEEE-half outputs                       (its epilogue)
                       gelu_poly2_f32    1.7e-5 on [-4.25, 4.25]; beyond, Phi is held at 1 - 7e-6 / 7e-6: 7e-6 |u| on top  (common.h)    fp32 outputs of gemm256 / gemm8p
                       gelu_poly2[_x8]   GELU_POLY2_ABS + GELU_POLY2_REL |want|, which already holds the 16-bit store      16-bit outputs of gemm256 / gemm8p
                       quick_gelu        x rcp(1 + exp(-1.702 x)): the argument's two products reach the result as 1.702 |x| 2^-23, one exp and one rcp at TR,
@@ -164,7 +164,7 @@ def dispatch(c):
 
 
 def epilogue256(c):
-    """which epilogue of gemm256_kernel a call takes (vec_ok / f32_ok, gemm.hip:296-297): "vector" (fast or predicated), "f32", or the "scalar" fallback"""
+    """which epilogue of gemm256_kernel a call takes (its vec_ok / f32_ok): "vector" (fast or predicated), "f32", or the "scalar" fallback"""
     if c.out == 16 and c.N % 8 == 0 and c.ldc % 8 == 0 and (not c.res or c.ldr % 8 == 0):
         return "vector"
     if c.out == 32 and c.N % 4 == 0 and c.ldc % 4 == 0 and (not c.res or c.ldr % 4 == 0):
@@ -173,7 +173,7 @@ def epilogue256(c):
 
 
 def fast_epilogue_runs(c):
-    """gemm256_kernel's fast epilogue (gemm.hip:573): no residual operand, vector stores, at least two k-steps, an interior tile of a block that has a NEXT tile --
+    """gemm256_kernel's fast epilogue (its fast_epi): no residual operand, vector stores, at least two k-steps, an interior tile of a block that has a NEXT tile --
     so more tiles than blocks.  True where some tile of the case takes it."""
     tiles = -(-c.M // 256) * -(-c.N // 256)
     return c.path == "g256" and not c.res and epilogue256(c) == "vector" and c.K >= 128 and tiles > N_CU and c.M >= 512 and c.N >= 512
@@ -183,14 +183,13 @@ def rounding_points(c):
     """Where a 16-bit result with a residual is rounded -> "once" or "twice".
 
     twice: act(y + bias) is rounded to the output type, the residual (read in that type) is added in fp32 and the sum is rounded again --
-        gemm256_kernel, fast epilogue        gemm.hip:609-610 (pack2bf) then 632-635
-        gemm256_kernel, vector epilogue      gemm.hip:714-715 then 727-730
+        gemm256_kernel, vector epilogue      gemm.hip: epi_bf16 (pack2bf), then the residual add of the predicated vector epilogue (the fast epilogue takes no residual)
         gemm8p_kernel                        gemm8p.hip:243-244 then 253-256
         gemm8p_pers_kernel                   gemm8p.hip:695 / 704-705 then 737-740 (explicit residual loads) or 765-768
     once: the residual is added to the fp32 value and the sum is rounded --
-        gemm_bf16_kernel                     gemm.hip:189-196
-        gemm256_kernel, scalar fallback      gemm.hip:812-819 (N % 8 != 0, ldc % 8 != 0 or ldr % 8 != 0)
-    fp32 outputs are never rounded to 16 bits (gemm.hip:186-187, 779-780, 809-810; gemm8p.hip:626, 664), and without a residual there is one store: once."""
+        gemm_bf16_kernel                     gemm.hip: the residual branch of its epilogue
+        gemm256_kernel, scalar fallback      gemm.hip: the residual branch of the scalar epilogue (N % 8 != 0, ldc % 8 != 0 or ldr % 8 != 0)
+    fp32 outputs are never rounded to 16 bits (gemm.hip: the out_f32 stores of gemm_bf16_kernel and of gemm256_kernel's fp32 and scalar epilogues; gemm8p.hip:626, 664), and without a residual there is one store: once."""
     if c.out == 32 or not c.res:
         return "once"
     if c.path in ("g8p_pers", "g8p_tile"):

@@ -12,8 +12,9 @@ batched products included -- and everything inside must have been written.  Ever
 relies on a fault.  The kernel each case must reach is asserted through sc_gemm_last_path() and the restated dispatcher (tests/test_gemm_bounds_cpu.py).
 The limit of that assertion: sc_gemm_last_path() tells gemm8p (3) and the vendor comparator (1) from the kernels of gemm.hip (0), and is set by sc_gemm_bf16 only.
 WHICH kernel of gemm.hip ran -- gemm256_kernel, its BATCH variant or gemm_bf16_kernel, and every batched call -- rests on the Python restatement of gemm_dispatch
-with the product library's constants (100 tiles; the batched entries never consult the vendor path).  A PROBES build reads SC_GEMM_MIN_TILES, SC_GEMM_V1 and
-SC_GEMM_NOBATCH256 from the environment and would choose differently, so every call asserts that they, and the comparator switch SC_GEMM_VENDOR, are unset.
+with the library's constants (100 tiles; the batched entries never consult the vendor path).  The dispatcher reads nothing from the environment any more (the
+PROBES build of earlier revisions read SC_GEMM_MIN_TILES, SC_GEMM_V1 and SC_GEMM_NOBATCH256 and would choose differently, so a run against such a library still
+asserts that they are unset); the comparator switch SC_GEMM_VENDOR must be unset.
 Each test prints its figures (-s); profiles/gemm_parity.txt holds the table of one run."""
 import os
 
