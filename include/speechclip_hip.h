@@ -789,6 +789,48 @@ int sc_topk_merge_items(const float* vals_in, const int64_t* idx_in, const int32
  *              aligned; K outside [1, 128]; R outside [K, 128]; N outside [1, 2^31); Q < 0; a null operand.  Q == 0 returns 0 and launches nothing. */
 int sc_search_rescore(const float* q, int64_t ld_q, const float* g, int64_t ld_g, int Q, int64_t N, int E, const int64_t* cand_idx, const float* short_vals,
                       int R, const float* eps, int K, int64_t idx_base, float* vals, int64_t* idx, int32_t* certified, void* stream);
+
+/* ---- Gallery search by threshold: every gallery row whose score reaches the query's threshold (csrc/search_range.hip) -- the other question a vector index
+ * is asked, answered like sc_search_topk without a [Q, N] score image.  The number of hits is not known beforehand, so there are TWO PASSES over the same
+ * scores: sc_search_range_count[_bf16] counts the hits of every (query, gallery range), the caller turns the counts into offsets with an exclusive scan (and
+ * learns the total T), and sc_search_range_fill[_bf16] recomputes the scores and writes every hit to its place.  The plain entries take fp32 rows, the _bf16
+ * entries bf16 rows; operands, strides, alignment and the rules for E are those of sc_search_topk and sc_search_topk_bf16 respectively.  thresh is f32 [Q].
+ * RANGE CONTRACT (restated on the host in tests/search_range_ref.py):
+ *   score     the plain entry's s(i, j) of the same format in every bit: fp32 rows the ascending fmaf chain of sc_search_topk on v_mfma_f32_32x32x2_f32,
+ *             bf16 rows the contract of sc_search_topk_bf16 (the same loading, staging and MFMA code is compiled into all of them; one accumulator per
+ *             (i, j), E never split).
+ *   hit       pair (i, j) is a hit iff s(i, j) >= thresh[i], compared in fp32, and the row is eligible.  A NaN score or a NaN threshold hits nothing;
+ *             thresh[i] = -inf hits every row whose score is not NaN; +inf hits only a score of +inf.
+ *   eligible  q_skip == NULL, or q_skip[i] < 0, or g_item[j] != q_skip[i] (g_item int32 [N], q_skip int32 [Q], as sc_search_items).  With a null q_skip
+ *             nothing reads g_item, which may then be null.  There is no `distinct` mode.
+ *   ranges    those of sc_search_topk: n_split ranges of ceil(N / n_split) rows, trailing ranges may be empty, one block per (query tile, range);
+ *             n_split = 0: sc_search_splits(Q, N, 1).  A query tile is 128 rows when Q > 64, else 64 (no list in LDS to make room for).
+ *   count     counts[i*ld_counts + s] (int32) = the number of hits of query i among the rows of range s, for every i in [0, Q) and s in [0, n_split); no
+ *             other element of `counts` is written, so with ld_counts > n_split several calls (the segments of an index) share one table, each writing
+ *             its own band of columns.
+ *   fill      the hits of (i, s), in ASCENDING j, go to vals[o] = s(i, j) / idx[o] = idx_base + j for o = offs[i*ld_offs + s] (int64), o + 1, ...  The
+ *             fill pass assumes nothing about the count pass except that the caller derived `offs` from its counts with the same operands and n_split:
+ *             with the exclusive scan over (i, s) in row-major order, query i's hits lie at [offs[i, 0], offs[i + 1, 0]) in ascending j.  Exactly
+ *             count(i, s) elements are written per (i, s); nothing else of vals / idx is touched.
+ *   pure      the hits of query i, their bits and their order depend on q[i, :E], g[:N, :E], thresh[i], the skip code and idx_base only: not on the other
+ *             queries, on n_split, on i's position in the call, or on what the outputs held before.  NO ATOMICS, global or LDS: a hit's place follows
+ *             from 64-bit ballots of the hit predicate (two query rows x 32 gallery columns per ballot) and their popcounts, a per-tile table of the four
+ *             column groups' counts per row in LDS, and a per-row running position.
+ *   reads     rows [0, Q) of q and [0, N) of g, E elements of each; thresh[0 .. Q); with q_skip: q_skip[0 .. Q) and g_item[0 .. N); fill: offs[i, s].
+ *   refused   (nonzero rc + sc_last_error naming the value, nothing launched) the E, ld_q / ld_g, alignment, N >= 2^31, n_split and Q < 0 rules of the
+ *             top-K entry of the same format; ld_counts / ld_offs below the split count; a null q, g, counts (count), offs, vals or idx (fill); a null
+ *             thresh; a non-null q_skip with a null g_item.  Q == 0 returns 0 and launches nothing.  (A caller whose total is 0 has nothing to fill and
+ *             does not call the fill pass.) */
+int sc_search_range_count(const float* q, int64_t ld_q, const float* g, int64_t ld_g, int Q, int64_t N, int E, const float* thresh, int n_split,
+                          const int32_t* g_item, const int32_t* q_skip, int32_t* counts, int64_t ld_counts, void* stream);
+int sc_search_range_fill(const float* q, int64_t ld_q, const float* g, int64_t ld_g, int Q, int64_t N, int E, const float* thresh, int n_split,
+                         const int32_t* g_item, const int32_t* q_skip, int64_t idx_base, const int64_t* offs, int64_t ld_offs, float* vals, int64_t* idx,
+                         void* stream);
+int sc_search_range_count_bf16(const void* q, int64_t ld_q, const void* g, int64_t ld_g, int Q, int64_t N, int E, const float* thresh, int n_split,
+                               const int32_t* g_item, const int32_t* q_skip, int32_t* counts, int64_t ld_counts, void* stream);
+int sc_search_range_fill_bf16(const void* q, int64_t ld_q, const void* g, int64_t ld_g, int Q, int64_t N, int E, const float* thresh, int n_split,
+                              const int32_t* g_item, const int32_t* q_skip, int64_t idx_base, const int64_t* offs, int64_t ld_offs, float* vals, int64_t* idx,
+                              void* stream);
 #ifdef __cplusplus
 }
 #endif

@@ -190,6 +190,10 @@ def _declare(L):
         "sc_search_items_bf16": ([P, L64, P, L64, I, L64, I, I, I, L64, P, P, I, P, P, P, P, P], c_int),
         "sc_topk_merge_items": ([P, P, P, I, I, I, I, P, P, P, P], c_int),
         "sc_search_rescore": ([P, L64, P, L64, I, L64, I, P, P, I, P, I, L64, P, P, P, P], c_int),
+        "sc_search_range_count": ([P, L64, P, L64, I, L64, I, P, I, P, P, P, L64, P], c_int),
+        "sc_search_range_fill": ([P, L64, P, L64, I, L64, I, P, I, P, P, L64, P, L64, P, P, P], c_int),
+        "sc_search_range_count_bf16": ([P, L64, P, L64, I, L64, I, P, I, P, P, P, L64, P], c_int),
+        "sc_search_range_fill_bf16": ([P, L64, P, L64, I, L64, I, P, I, P, P, L64, P, L64, P, P, P], c_int),
     }
     for name, (args, res) in sigs.items():
         fn = getattr(L, name)   # AttributeError here = header/library mismatch: fail loudly

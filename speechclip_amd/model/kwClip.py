@@ -150,6 +150,12 @@ class KWClipBase(BaseLightningModel):
         (hard negatives: the nearest items that are not the query's own); rerank=R: the same result by the two-stage search of an index with a shadow."""
         return index.search(self._embed(images=images, sents=sents, wav=wav), k, distinct=distinct, exclude=exclude, rerank=rerank)
 
+    def search_range(self, index: EmbeddingIndex, min_score, images=None, sents=None, wav=None, exclude=None, max_results=None):
+        """Every item of `index` that scores at least min_score (one number, or one per query) for every query of one modality -> (lims i64 [Q + 1],
+        scores f32 [T], positions i64 [T], ids): query i's hits are lims[i]:lims[i + 1] in ascending position (EmbeddingIndex.search_range).  exclude: one
+        id per query to leave out; max_results: the most hits to return before ValueError (default: 1 GiB of results)."""
+        return index.search_range(self._embed(images=images, sents=sents, wav=wav), min_score, exclude=exclude, max_results=max_results)
+
     def forward(self, batch: dict) -> tuple:
         raise NotImplementedError()
 

@@ -62,7 +62,9 @@ class EmbeddingIndex:
     segments, positions, ids and merge, and the same one-segment equality.  The default stays fp32.
     shadow=True (fp32 storage, dim % 16 == 0) keeps, beside every fp32 segment, the same rows rounded to bf16 -- exactly what astype("bf16") holds -- and the
     running maximum of the stored rows' norms: what search(..., rerank=R) needs to answer with the fp32 result at close to the bf16 search's cost.
-    There is no host implementation: without the library's GPU `add` / `search` raise SpeechClipHipError, like mutualRetrieval."""
+    search_range answers the other question -- "which stored items score at least t for this query?" -- with the same scores (sc_search_range_count /
+    sc_search_range_fill: two passes, no score image, hits in ascending position), on either storage.
+    There is no host implementation: without the library's GPU `add` / `search` / `search_range` raise SpeechClipHipError, like mutualRetrieval."""
 
     STORAGES = {"fp32": torch.float32, "bf16": torch.bfloat16}
     STORAGE_BITS = {"fp32": 32, "bf16": 16}            # how state_dict names the storage
@@ -248,6 +250,44 @@ class EmbeddingIndex:
             scores, pos = scores.index_copy(0, rows, s2), pos.index_copy(0, rows, p2)
         out = (scores, pos, self._ids_of(pos))
         return out + (certified,) if return_certified else out
+
+    def search_range(self, queries: torch.Tensor, min_score, exclude: Optional[Sequence[Hashable]] = None, max_results: Optional[int] = None):
+        """Every stored row that scores at least min_score -> (lims i64 [Q + 1], scores f32 [T], positions i64 [T], ids list [T]): query i's hits are
+        lims[i]:lims[i + 1], in ascending position, with the scores of `search` bit for bit.  min_score: one float, or one value per query (a sequence or
+        a tensor of len(queries)); a NaN hits nothing, -inf hits every row.  exclude: one id per query, as in `search`.  No [Q, N] score image: every
+        segment counts its hits into its own columns of one table (sc_search_range_count), ONE scan and ONE read of the total follow, then every segment
+        writes its hits with its starting position as idx_base (sc_search_range_fill) -- so the result equals that of one segment holding the
+        concatenation, bit for bit and position for position.  More than max_results hits (default: 1 GiB of results) raise ValueError before anything
+        is allocated or written.  An index with a shadow searches its fp32 rows."""
+        from .. import ops
+        dev = self._device()
+        codes, skip = self._item_arguments(queries, 1, False, exclude) if exclude is not None else ([None] * len(self.segments), None)
+        q = self._rows(queries)
+        Q = q.shape[0]
+        thresh = torch.as_tensor(min_score, dtype=torch.float32).to(dev)
+        if thresh.dim() == 0:
+            thresh = thresh.expand(Q)
+        if thresh.shape != (Q,):
+            raise ValueError(f"min_score must be one number or one per query ({Q}), got shape {tuple(thresh.shape)}")
+        thresh = thresh.contiguous()
+        if skip is not None:
+            skip = torch.tensor(skip, dtype=torch.int32, device=dev)
+        splits = [ops.lib().sc_search_splits(Q, seg.shape[0], 1) for seg in self.segments]
+        counts = torch.empty(Q, sum(splits), device=dev, dtype=torch.int32)
+        at = 0
+        for seg, code, S in zip(self.segments, codes, splits):
+            ops.search_range_count(q, seg, thresh, S, code, skip, out=counts[:, at:at + S])
+            at += S
+        lims, offs, total = ops.search_range_offsets(counts, max_results)
+        scores = torch.empty(total, device=dev, dtype=torch.float32)
+        pos = torch.empty(total, device=dev, dtype=torch.int64)
+        at = base = 0
+        for seg, code, S in zip(self.segments, codes, splits):
+            ops.search_range_fill(q, seg, thresh, offs[:, at:at + S], scores, pos, S, base, code, skip)
+            at += S
+            base += seg.shape[0]
+        host = pos.cpu().tolist()
+        return lims, scores, pos, host if self.ids is None else [self.ids[p] for p in host]
 
     def _ids_of(self, pos: torch.Tensor) -> list:
         host = pos.cpu().tolist()

@@ -1176,6 +1176,98 @@ def search_rescore(q, g, cand_idx, short_vals, eps, k, idx_base=0):
     return vals, idx, certified
 
 
+# ---- gallery search by threshold (search_range.hip) ----
+RANGE_MAX_RESULTS = (1 << 30) // 12        # the hits whose 12 bytes each (f32 score + i64 index) fit in 1 GiB
+
+
+def _range_operands(q, g, thresh, n_split, g_item, q_skip):
+    """The checks shared by the two passes -> (entry suffix, Q, N, E, split count)."""
+    _need_cuda(q, g, thresh)
+    assert q.dtype in (torch.float32, bf16) and g.dtype == q.dtype and q.dim() == 2 and g.dim() == 2 and q.stride(1) == 1 and g.stride(1) == 1, (q.dtype, g.dtype)
+    assert q.shape[1] == g.shape[1], (q.shape, g.shape)
+    Q, E = q.shape
+    N = g.shape[0]
+    assert thresh.dtype == torch.float32 and thresh.shape == (Q,) and thresh.is_contiguous(), (thresh.dtype, thresh.shape)
+    if q_skip is not None:
+        assert g_item is not None, "q_skip needs g_item"
+        _need_cuda(g_item, q_skip)
+        assert g_item.dtype == torch.int32 and g_item.shape == (N,) and g_item.is_contiguous(), (g_item.dtype, g_item.shape)
+        assert q_skip.dtype == torch.int32 and q_skip.shape == (Q,) and q_skip.is_contiguous(), (q_skip.dtype, q_skip.shape)
+    S = int(n_split) if n_split else lib().sc_search_splits(Q, N, 1)
+    return ("_bf16" if q.dtype == bf16 else ""), Q, N, E, S
+
+
+def search_range_count(q, g, thresh, n_split=0, g_item=None, q_skip=None, out=None):
+    """The first pass of search_range (sc_search_range_count[_bf16], by the rows' dtype) -> counts i32 [Q, S]: the hits of every query in every gallery
+    range, S = n_split or sc_search_splits(Q, N, 1).  `out`: an int32 [Q, S] view with unit column stride (a band of columns of a wider table that the
+    segments of an index share); nothing outside it is written.  Default: allocated here."""
+    sfx, Q, N, E, S = _range_operands(q, g, thresh, n_split, g_item, q_skip)
+    if out is None:
+        out = torch.empty(Q, S, device=q.device, dtype=torch.int32)
+    assert out.is_cuda and out.dtype == torch.int32 and out.shape == (Q, S) and (out.stride(1) == 1 or S == 1), (out.dtype, out.shape, out.stride())
+    name = "sc_search_range_count" + sfx
+    check(getattr(lib(), name)(ptr(q), q.stride(0), ptr(g), g.stride(0), Q, N, E, ptr(thresh), int(n_split), ptr(g_item if q_skip is not None else None),
+                               ptr(q_skip), ptr(out), out.stride(0) if Q > 1 else max(out.stride(0), S), stream()), name)
+    return out
+
+
+def search_range_offsets(counts, max_results=None):
+    """counts i32 [Q, S] (contiguous: one table for the whole gallery) -> (lims i64 [Q + 1], offs i64 [Q, S], T): the exclusive scan over (query, range) in
+    row-major order -- plumbing, torch.cumsum -- and the total, whose read is the ONE host synchronisation of a search by threshold.  More than
+    max_results hits (default RANGE_MAX_RESULTS, 1 GiB of results) raise ValueError here, before anything is allocated or filled."""
+    assert counts.dtype == torch.int32 and counts.dim() == 2 and counts.is_contiguous()
+    Q, S = counts.shape
+    limit = RANGE_MAX_RESULTS if max_results is None else int(max_results)
+    if Q == 0 or S == 0:
+        return torch.zeros(Q + 1, device=counts.device, dtype=torch.int64), torch.zeros(Q, S, device=counts.device, dtype=torch.int64), 0
+    ends = torch.cumsum(counts.reshape(-1), 0, dtype=torch.int64)
+    offs = (ends - counts.reshape(-1)).view(Q, S)
+    lims = torch.cat([offs[:, 0], ends[-1:]])
+    total = int(ends[-1])
+    if total > limit:
+        raise ValueError(f"search_range: {total} hits exceed max_results={limit}; raise the threshold, pass fewer queries or a larger max_results")
+    return lims, offs, total
+
+
+def search_range_fill(q, g, thresh, offs, vals, idx, n_split=0, idx_base=0, g_item=None, q_skip=None):
+    """The second pass (sc_search_range_fill[_bf16]): the hits of (query i, range s) go to vals f32 [T] / idx i64 [T] from offs[i, s] on, in ascending row
+    order, idx = idx_base + row.  offs: an int64 [Q, S] view with unit column stride, derived from the counts of the same operands and n_split."""
+    sfx, Q, N, E, S = _range_operands(q, g, thresh, n_split, g_item, q_skip)
+    _need_cuda(offs, vals, idx)
+    assert offs.dtype == torch.int64 and offs.shape == (Q, S) and (offs.stride(1) == 1 or S == 1), (offs.dtype, offs.shape, offs.stride())
+    assert vals.dtype == torch.float32 and idx.dtype == torch.int64 and vals.dim() == 1 and vals.shape == idx.shape and vals.is_contiguous() and idx.is_contiguous()
+    if vals.numel() == 0:
+        return
+    name = "sc_search_range_fill" + sfx
+    check(getattr(lib(), name)(ptr(q), q.stride(0), ptr(g), g.stride(0), Q, N, E, ptr(thresh), int(n_split), ptr(g_item if q_skip is not None else None),
+                               ptr(q_skip), int(idx_base), ptr(offs), offs.stride(0) if Q > 1 else max(offs.stride(0), S), ptr(vals), ptr(idx), stream()), name)
+
+
+def _search_range(dtype, q, g, thresh, n_split, idx_base, g_item, q_skip, max_results):
+    _need_cuda(q, g)
+    assert q.dtype == dtype and g.dtype == dtype, (q.dtype, g.dtype)
+    counts = search_range_count(q, g, thresh, n_split, g_item, q_skip)
+    lims, offs, total = search_range_offsets(counts, max_results)
+    vals = torch.empty(total, device=q.device, dtype=torch.float32)
+    idx = torch.empty(total, device=q.device, dtype=torch.int64)
+    search_range_fill(q, g, thresh, offs, vals, idx, n_split, idx_base, g_item, q_skip)
+    return lims, vals, idx
+
+
+def search_range(q, g, thresh, n_split=0, idx_base=0, g_item=None, q_skip=None, max_results=None):
+    """q f32 [Q, E], g f32 [N, E] (device, last stride 1), thresh f32 [Q] -> (lims i64 [Q + 1], vals f32 [T], idx i64 [T]): query i's hits -- every gallery
+    row whose fp32 fmaf-chain score (search_topk's, bit for bit) is >= thresh[i] -- lie at lims[i]:lims[i + 1] in ascending row order, idx = idx_base + row.
+    A NaN score or threshold hits nothing.  g_item i32 [N] / q_skip i32 [Q]: rows carrying the query's skip code (>= 0) are left out, as search_items.
+    No [Q, N] score image: a count pass, torch.cumsum, one read of the total, exactly T entries allocated, a fill pass (sc_search_range_count / _fill).
+    More than max_results hits (default: 1 GiB of results) raise ValueError before anything is allocated."""
+    return _search_range(torch.float32, q, g, thresh, n_split, idx_base, g_item, q_skip, max_results)
+
+
+def search_range_bf16(q, g, thresh, n_split=0, idx_base=0, g_item=None, q_skip=None, max_results=None):
+    """search_range on bf16 rows (E % 16 == 0): search_topk_bf16's scores under the same rule (sc_search_range_count_bf16 / _fill_bf16)."""
+    return _search_range(bf16, q, g, thresh, n_split, idx_base, g_item, q_skip, max_results)
+
+
 # ---- cascaded tail, training (train_cascaded.hip) ----
 def attn_small_bwd(qkv16, dout, B, L, H, causal=True):
     """qkv bf16 [B*L, 3*H*64] (saved by the forward), dout f32 [B*L, H*64] -> dqkv f32 [B*L, 3*H*64]."""
