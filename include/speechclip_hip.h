@@ -399,7 +399,8 @@ int sc_cosine_bwd_finish(const float* a, const float* G, const float* rowdot, fl
  *   h = hash32(seed ^ hash32(idx + 0x9e3779b9)) with hash32(x): x ^= x >> 16; x *= 0x7feb352d; x ^= x >> 15; x *= 0x846ca68b; x ^= x >> 16 (the dropout hash),
  *   u = ((h >> 9) + 0.5) * 2^-23 (exact in fp32, in [2^-24, 1 - 2^-24]), e = -log u (the Exponential(1) draw of F.gumbel_softmax), g = -log e in [-2.82, 16.64];
  *   both logarithms are the accurate logf.  Every entry: seed_on = 0 means g = 0 (seed ignored); mask ids as in sc_vq_st_bwd (at most 8); no atomics, results
- *   bitwise identical run to run.
+ *   bitwise identical run to run.  A row with EVERY column masked (V <= 8) has y = 0: sc_vq_probs writes a row of zeros, sc_vq_soft_embed a zero keyword row
+ *   with row_max = -inf and row_den = 0, sc_vq_mode_bwd dcos = 0 and both rowdots 0, sc_vq_noisy_argmax target 0.
  * sc_vq_gumbel_noise: out f32 [R,V] = g.
  * sc_vq_noisy_argmax: targets[r] = arg-max_v (x + g) over the unmasked sub-words, the lowest index on ties.
  * sc_vq_probs: out f32 [R,V] = y (dense; for the lazy `subword_prob` and for shapes sc_vq_soft_embed does not cover).
