@@ -2,6 +2,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include "../../include/speechclip_hip.h"
 
 typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8_t;
 typedef __attribute__((ext_vector_type(4))) __bf16 bf16x4_t;
@@ -234,6 +235,31 @@ __device__ __forceinline__ uint32_t hash_pair(uint32_t seed, uint32_t pair_idx) 
 static inline uint32_t drop_thresh16(float pd) { return pd <= 0.f ? 0u : (uint32_t)fmin(65535.0, (double)pd * 65536.0); }
 // CLIP QuickGELU: x * sigmoid(1.702 x)
 __device__ __forceinline__ float quick_gelu(float x) { return x * __builtin_amdgcn_rcpf(1.0f + __expf(-1.702f * x)); }
+
+// What the GEMM kernels (gemm.hip, gemm8p.hip) share.
+// LDS-DMA: 16 bytes per lane from global memory straight into LDS, lane L to lds_wave_base + 16 L.
+__device__ __forceinline__ void glds16(const void* gsrc, void* lds_wave_base) {
+    __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)gsrc,
+                                     (__attribute__((address_space(3))) void*)lds_wave_base, 16, 0, 0);
+}
+// The activation (ACT: SC_ACT_*) of a GEMM epilogue on four consecutive results of a row, the one statement of it.  F32: the fp32 polynomial of GELU for
+// fp32 outputs (the packed-half form carries ~11 bits, meant for 16-bit results).
+template <int ACT, bool F32>
+__device__ __forceinline__ f32x4_t epi_act(f32x4_t v4) {
+    if (ACT == SC_ACT_GELU) {
+        const f32x2_t g0 = F32 ? gelu_poly2_f32((f32x2_t){v4[0], v4[1]}) : gelu_poly2((f32x2_t){v4[0], v4[1]});
+        const f32x2_t g1 = F32 ? gelu_poly2_f32((f32x2_t){v4[2], v4[3]}) : gelu_poly2((f32x2_t){v4[2], v4[3]});
+        v4 = (f32x4_t){g0[0], g0[1], g1[0], g1[1]};
+    } else if (ACT == SC_ACT_QUICKGELU) {
+#pragma unroll
+        for (int r = 0; r < 4; ++r) v4[r] = quick_gelu(v4[r]);
+    }
+    return v4;
+}
+// Residual add on one packed pair of 16-bit results: o + r in fp32, rounded again.
+template <bool F16> __device__ __forceinline__ uint32_t add_packed(uint32_t o, uint32_t r) {
+    return pack2x<F16>(lo2fx<F16>(o) + lo2fx<F16>(r), hi2fx<F16>(o) + hi2fx<F16>(r));
+}
 
 __device__ __forceinline__ float wave_sum(float v) {
 #pragma unroll

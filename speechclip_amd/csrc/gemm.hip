@@ -35,10 +35,6 @@ struct GemmParams {
 
 constexpr int BK = 64;  // 128 bytes of bf16 per tile row = 8 chunks of 16 B
 
-__device__ __forceinline__ void glds16(const void* gsrc, void* lds_wave_base) {
-    __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)gsrc,
-                                     (__attribute__((address_space(3))) void*)lds_wave_base, 16, 0, 0);
-}
 // This file holds the kernels that ship, in the one configuration that ships.  Every measured variant -- the operand cache-policy (nt / sc bits on
 // the LDS-DMA pieces), buffer-form DMA, wave-priority and DMA-placement forms of rounds 1-2, the ablations, the two-slot ring, the other epilogue
 // modes and store forms, the delayed block starts, the per-phase cycle trace and the environment knobs of the dispatcher -- is recorded with its numbers in
@@ -214,22 +210,7 @@ struct StageAddr { const bf16_t* ta; const bf16_t* tw; };
 constexpr int HALF_SLOT = 256 * 128;                            // one operand of one stage: 256 rows x 128 B
 constexpr int LDS256 = 5 * HALF_SLOT;                           // A0 A1 A2 W0 W1
 
-// Accumulator + bias -> activation, the one statement of the epilogue arithmetic.  F32: the fp32 polynomial of GELU for fp32 outputs (the packed-half
-// form carries ~11 bits, meant for bf16 results).
-template <int ACT, bool F32>
-__device__ __forceinline__ f32x4_t epi_act(f32x4_t acc, f32x4_t bias) {
-    f32x4_t v4 = acc + bias;
-    if (ACT == SC_ACT_GELU) {
-        const f32x2_t g0 = F32 ? gelu_poly2_f32((f32x2_t){v4[0], v4[1]}) : gelu_poly2((f32x2_t){v4[0], v4[1]});
-        const f32x2_t g1 = F32 ? gelu_poly2_f32((f32x2_t){v4[2], v4[3]}) : gelu_poly2((f32x2_t){v4[2], v4[3]});
-        v4 = (f32x4_t){g0[0], g0[1], g1[0], g1[1]};
-    } else if (ACT == SC_ACT_QUICKGELU) {
-#pragma unroll
-        for (int r = 0; r < 4; ++r) v4[r] = quick_gelu(v4[r]);
-    }
-    return v4;
-}
-// Row block of a wave's results: bias / activation -> bf16 pairs (epi_bf16), then transposed for full-row stores (epi_transpose).  Lane (frow, fk) holds row frow, columns 16j + 4fk .. +3 of each 16-column
+// Row block of a wave's results: bias / activation (epi_act, common.h) -> bf16 pairs (epi_bf16), then transposed for full-row stores (epi_transpose).  Lane (frow, fk) holds row frow, columns 16j + 4fk .. +3 of each 16-column
 // block j.  v_permlane16_swap between the 16-lane rows fk and fk^1 regroups a block PAIR (j0, j1) so that even-fk lanes own 8 consecutive columns
 // of j0 and odd-fk lanes 8 consecutive columns of j1 (16 bytes per lane).  Stored from there, the four lanes of every lane QUAD would hit four
 // different rows, and the store path handles a wave quad by quad: 13 B/clk/CU measured, against 24-36 B/clk/CU when a quad covers 64 contiguous
@@ -238,7 +219,7 @@ __device__ __forceinline__ f32x4_t epi_act(f32x4_t acc, f32x4_t bias) {
 // bytes.  bperm = ((lane row that holds this chunk after the swap) * 16 + L >> 2) << 2.
 template <int ACT>
 __device__ __forceinline__ uint2 epi_bf16(f32x4_t acc, f32x4_t bias) {     // ... -> pack to bf16: four consecutive columns of one row
-    const f32x4_t v4 = epi_act<ACT, false>(acc, bias);
+    const f32x4_t v4 = epi_act<ACT, false>(acc + bias);
     return make_uint2(pack2bf(v4[0], v4[1]), pack2bf(v4[2], v4[3]));
 }
 __device__ __forceinline__ uint4 epi_transpose(const uint2 (&pk)[4], int jp, int bperm) {
@@ -599,10 +580,7 @@ __global__ __launch_bounds__(512) void gemm256_kernel(GemmParams p) {
                     if (m >= m_lo && n >= n_lo) {
                         if (RES) {
                             const uint4 rv = res[i & 3][jp];
-                            o.x = pack2bf(lo2f(o.x) + lo2f(rv.x), hi2f(o.x) + hi2f(rv.x));
-                            o.y = pack2bf(lo2f(o.y) + lo2f(rv.y), hi2f(o.y) + hi2f(rv.y));
-                            o.z = pack2bf(lo2f(o.z) + lo2f(rv.z), hi2f(o.z) + hi2f(rv.z));
-                            o.w = pack2bf(lo2f(o.w) + lo2f(rv.w), hi2f(o.w) + hi2f(rv.w));
+                            o.x = add_packed<false>(o.x, rv.x); o.y = add_packed<false>(o.y, rv.y); o.z = add_packed<false>(o.z, rv.z); o.w = add_packed<false>(o.w, rv.w);
                         }
                         *(uint4*)(Cb + m * p.ldc + n) = o;
                     }
@@ -634,7 +612,7 @@ __global__ __launch_bounds__(512) void gemm256_kernel(GemmParams p) {
                 f32x4_t o[4];
 #pragma unroll
                 for (int j = 0; j < 4; ++j) {
-                    const f32x4_t v4 = epi_act<ACT, true>(acc[i][j], bias4[j]);
+                    const f32x4_t v4 = epi_act<ACT, true>(acc[i][j] + bias4[j]);
 #pragma unroll
                     for (int r = 0; r < 4; ++r) { const float t = v4[r]; o[j][r] = __int_as_float(__builtin_amdgcn_ds_bpermute(bperm, __float_as_int(t))); }
                 }
@@ -657,7 +635,7 @@ __global__ __launch_bounds__(512) void gemm256_kernel(GemmParams p) {
                 for (int j = 0; j < 4; ++j) {
                     const int n = n0 + wn * 64 + j * 16 + fk * 4;
                     if (n < n_lo) continue;
-                    f32x4_t v4 = p.out_f32 ? epi_act<ACT, true>(acc[i][j], bias4[j]) : epi_act<ACT, false>(acc[i][j], bias4[j]);
+                    f32x4_t v4 = p.out_f32 ? epi_act<ACT, true>(acc[i][j] + bias4[j]) : epi_act<ACT, false>(acc[i][j] + bias4[j]);
                     if (p.out_f32) {
                         if (p.residual) v4 += *(const f32x4_t*)((const float*)p.residual + m * p.ldr + n);
                         *(f32x4_t*)((float*)Cb + m * p.ldc + n) = v4;
@@ -749,7 +727,7 @@ int launch(const GemmParams& p, int batch, hipStream_t s) {
 }
 
 // The argument rules of every hand-written GEMM kernel, stated once: the three entry points check them before they choose a kernel
-// (sc_gemm_bf16: before the ping-pong kernels of gemm8p.hip as well as before gemm_dispatch).
+// (sc_gemm_bf16: before the ping-pong kernel of gemm8p.hip as well as before gemm_dispatch).
 int check_gemm_args(const GemmParams& p, int batch) {
     SC_CHECK_ARG(p.K > 0 && p.K % 64 == 0, "sc_gemm: K=%d must be a positive multiple of 64", p.K);
     SC_CHECK_ARG(p.N > 0 && p.N % 4 == 0, "sc_gemm: N=%d must be a positive multiple of 4", p.N);
@@ -806,21 +784,17 @@ static int g_last_path = 0;   // 0: gemm256_kernel / gemm_bf16_kernel, 1: vendor
 extern "C" int sc_gemm_last_path(void) { return g_last_path; }
 // Kernel choice behind sc_gemm_bf16 (developer / test switch, exported but not part of include/speechclip_hip.h):
 //   -1 the dispatcher's rule (default)   0 gemm256_kernel / gemm_bf16_kernel only   16 gemm8p whenever the shape allows   26 gemm8p with the static tile order
-// The round-5 A/B variants (17 per-tile launch, 19 / 24 / 25 K rotations, 20 tap-paired K walk, 21-23 forced column bands) exist only in a -DSC_LAB=1 build
-// (tools/build_ab.sh); the product library maps them to the default.
-#ifndef SC_LAB
-#define SC_LAB 0
-#endif
+// Anything else is the default.
 #ifndef SC_GEMM_MODE_DEFAULT
 #define SC_GEMM_MODE_DEFAULT -1
 #endif
 static int g_gemm_mode = SC_GEMM_MODE_DEFAULT;
-extern "C" void sc_debug_set_gemm_mode(int mode) { g_gemm_mode = (SC_LAB || mode == -1 || mode == 0 || mode == 16 || mode == 26) ? mode : -1; }
+extern "C" void sc_debug_set_gemm_mode(int mode) { g_gemm_mode = (mode == -1 || mode == 0 || mode == 16 || mode == 26) ? mode : -1; }
 #ifndef SC_PROBES
 #define SC_PROBES 0
 #endif
 static unsigned long long* g_gemm_trace = nullptr;
-// per-block cycle stamps of the ping-pong kernels (gemm8p.hip): effective only in the PROBES build
+// per-block cycle stamps of the ping-pong kernel (gemm8p.hip): effective only in the PROBES build
 extern "C" void sc_debug_set_gemm_trace(void* dev_buf) { g_gemm_trace = SC_PROBES ? (unsigned long long*)dev_buf : nullptr; }
 
 extern "C" int sc_gemm_bf16(const void* A, int64_t lda, const void* W, int64_t ldw, void* C, int64_t ldc,
@@ -849,16 +823,10 @@ extern "C" int sc_gemm_bf16(const void* A, int64_t lda, const void* W, int64_t l
         d.A = (const bf16_t*)A; d.lda = lda; d.W = (const bf16_t*)W; d.ldw = ldw; d.C = C; d.ldc = ldc; d.out_f32 = (flags & SC_GEMM_OUT_F32) ? 1 : 0;
         d.bias = bias; d.residual = residual; d.ldr = ldr; d.M = M; d.N = N; d.K = K;
         d.act = flags & SC_GEMM_ACT_MASK; d.f16 = f16;
-        d.esteps = 4; d.trace = g_gemm_trace;
+        d.trace = g_gemm_trace;
         // column-band tile order: wide outputs (>= 16 N tiles: 8192^3 1 444 vs 1 323 TF/s unbanded, gemm256_kernel 1 406; HuBERT-large fc1 +2 %) walk 4 N tiles at a time
         d.band = (g_gemm_mode == -1 && N / 256 >= 16) ? 4 : 0;
-        d.sched = g_gemm_mode == 26 ? -1 : 0;      // 26: static tile order (A/B, and the reference of the dynamic order's bit-identity test)
-#if SC_LAB
-        d.kpair = (g_gemm_mode == 20 && lda < K && K == 3 * (lda / 2) && (lda / 2) % 64 == 0) ? (int)(lda / 2 / 64) : 0;      // tap-paired K walk
-        if (g_gemm_mode == 17) d.esteps = 1;                                                                                     // per-tile kernel
-        d.rows = g_gemm_mode == 19 ? 1 : g_gemm_mode == 24 ? 2 : g_gemm_mode == 25 ? 3 : 0;                                      // K rotations
-        if (g_gemm_mode >= 21 && g_gemm_mode <= 23) d.band = g_gemm_mode == 21 ? 3 : g_gemm_mode == 22 ? 4 : 6;                  // forced column bands
-#endif
+        d.sched = g_gemm_mode == 26 ? -1 : 0;      // 26: static tile order (the reference of the dynamic order's bit-identity test)
         // (the kernel copies the bias vector with 16-byte loads and reads the residual in 16-byte pieces)
         const bool aligned = (!residual || ((uintptr_t)residual & 15) == 0) && (!bias || ((uintptr_t)bias & 15) == 0);
         const bool dflt_ok = N % 256 == 0 && N <= 8192 && ((M + 255) / 256) * (int64_t)(N / 256) >= 128;

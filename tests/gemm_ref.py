@@ -1,5 +1,5 @@
 """Plain fp64 statements, case lists per dispatch path, deterministic inputs, the per-path rounding model and DERIVED per-element bounds of the 16-bit GEMM kernels
-(csrc/gemm.hip: gemm_bf16_kernel<128,64 / 128,128, F16>, gemm256_kernel and its BATCH variant; csrc/gemm8p.hip: gemm8p_pers_kernel, gemm8p_kernel) for
+(csrc/gemm.hip: gemm_bf16_kernel<128,64 / 128,128, F16>, gemm256_kernel and its BATCH variant; csrc/gemm8p.hip: gemm8p_pers_kernel) for
 tests/test_gemm_parity_gpu.py and tools/gemm_bounds.py.  A helper module, not a test; no kernel runs here.  The constants, the generator, the rounding helper, the
 guarded window and the judge are those of tests/row_kernels_ref.py and are imported, not restated.
 
@@ -22,7 +22,7 @@ The bound of a real case, per element (U = 2^-24, TR = 2^-22, BF_STORE, H16_STOR
     products        two 8-bit (bf16) or 11-bit (half) significands: exact in fp32
     accumulation    K u_acc sum_k |a_k w_k| with u_acc = 2^-23, the sum through a second fp64 product of the absolute values.  The chain is taken as K additions;
                     no ISA document is on hand for the rounding of the matrix core's internal adds, so one factor 2 over U is BUDGETED, as TR was.
-                    gemm8p_pers_kernel starts its accumulators FROM the bias (SC_8P_BIAS_INIT, gemm8p.hip:443): the bias then sits in each of the K / 32
+                    gemm8p_pers_kernel starts its accumulators FROM the bias (its init_q): the bias then sits in each of the K / 32
                     accumulator updates, (K / 32) u_acc |bias| on top.
     bias, residual  one U |result| each
     activation      the pre-activation's error through |gelu'| <= GELU_LIP (1.13; QuickGELU's largest slope is 1.10), plus the form's own constant:
@@ -56,7 +56,7 @@ PAD = 4096                                  # NaN elements in front of and behin
 ORDERS = ("seq", "rot32")
 
 GemmCase = collections.namedtuple("GemmCase", "id path mode api kind M N K lda ldw ldc ldr act bias res out f16 S w_mod inner also")
-PATHS = ("bf128x64", "bf128x128", "h128x64", "h128x128", "g256", "g256_batch", "bf128_batched", "g8p_pers", "g8p_tile")
+PATHS = ("bf128x64", "bf128x128", "h128x64", "h128x128", "g256", "g256_batch", "bf128_batched", "g8p_pers")
 ROWS128 = ("bf128x64", "bf128x128", "h128x64", "h128x128", "bf128_batched")
 
 
@@ -86,9 +86,7 @@ def nprod(c):
 def gemm8p_try(c, mode):
     """sc_gemm8p_try (gemm8p.hip): None where it declines, else (path, tile order, column band)"""
     f32 = c.out == 32
-    if c.N % 256 or c.K % 64 or c.M < 256:
-        return None
-    if c.M % 256 and c.N > 8192:
+    if c.N % 256 or c.N > 8192 or c.K % 64 or c.M < 256:
         return None
     nk = c.K // 64
     if nk < 2:
@@ -98,13 +96,9 @@ def gemm8p_try(c, mode):
         return None
     tiles = -(-c.M // 256) * (c.N // 256)
     band = 4 if (mode == -1 and c.N // 256 >= 16) else 0
-    if c.N <= 8192:
-        pg = min(tiles, N_CU)
-        dyn = mode != 26 and nk >= 6 and c.N < 8192 and pg >= 8
-        return "g8p_pers", ("dyn" if dyn else "static"), band
-    if f32 or c.f16:
-        return None
-    return "g8p_tile", "static", 0
+    pg = min(tiles, N_CU)
+    dyn = mode != 26 and nk >= 6 and c.N < 8192 and pg >= 8
+    return "g8p_pers", ("dyn" if dyn else "static"), band
 
 
 def gemm_dispatch(c, batch):
@@ -184,15 +178,14 @@ def rounding_points(c):
 
     twice: act(y + bias) is rounded to the output type, the residual (read in that type) is added in fp32 and the sum is rounded again --
         gemm256_kernel, vector epilogue      gemm.hip: epi_bf16 (pack2bf), then the residual add of the predicated vector epilogue (the fast epilogue takes no residual)
-        gemm8p_kernel                        gemm8p.hip:243-244 then 253-256
-        gemm8p_pers_kernel                   gemm8p.hip:695 / 704-705 then 737-740 (explicit residual loads) or 765-768
+        gemm8p_pers_kernel                   gemm8p.hip: `shuffled` (pack2x) of the 16-bit epilogue, then add_packed behind the explicit residual loads
     once: the residual is added to the fp32 value and the sum is rounded --
         gemm_bf16_kernel                     gemm.hip: the residual branch of its epilogue
         gemm256_kernel, scalar fallback      gemm.hip: the residual branch of the scalar epilogue (N % 8 != 0, ldc % 8 != 0 or ldr % 8 != 0)
-    fp32 outputs are never rounded to 16 bits (gemm.hip: the out_f32 stores of gemm_bf16_kernel and of gemm256_kernel's fp32 and scalar epilogues; gemm8p.hip:626, 664), and without a residual there is one store: once."""
+    fp32 outputs are never rounded to 16 bits (gemm.hip: the out_f32 stores of gemm_bf16_kernel and of gemm256_kernel's fp32 and scalar epilogues; gemm8p.hip: both arms of the F32 epilogue), and without a residual there is one store: once."""
     if c.out == 32 or not c.res:
         return "once"
-    if c.path in ("g8p_pers", "g8p_tile"):
+    if c.path == "g8p_pers":
         return "twice"
     if c.path == "g256" and epilogue256(c) == "vector":
         return "twice"
@@ -243,7 +236,11 @@ def cases_bf128x128():
             _c("bf-r-2400x2304x64-below100", "bf128x128", -1, "real", 2400, 2304, 64, res=True, also="below100"),
             _c("bf-x-2400x2304x128-below100", "bf128x128", -1, "exact", 2400, 2304, 128, out=32, res=True, also="below100"),
             _c("bf-r-257x132x128-ldw", "bf128x128", -1, "real", 257, 132, 128, ldw=136, lda=136, res=True, ldc=140, ldr=136, also="ldw"),
-            _c("bf-r-300x260x192-conv", "bf128x128", -1, "real", 300, 260, 192, lda=64, also="overlap")]
+            _c("bf-r-300x260x192-conv", "bf128x128", -1, "real", 300, 260, 192, lda=64, also="overlap"),
+            # mode 16 and N > 8192: sc_gemm8p_try declines (the bias vector of gemm8p_pers_kernel sits in LDS), 33 tiles go to this kernel.  (The ids, and with
+            # them the inputs, are those the cases had when a per-tile ping-pong kernel answered for them.)
+            _c("g8p-tile-x-256x8448x128", "bf128x128", 16, "exact", 256, 8448, 128, also="declined8p"),
+            _c("g8p-tile-r-256x8448x128", "bf128x128", 16, "real", 256, 8448, 128, res=True, also="declined8p")]
     return out
 
 
@@ -337,9 +334,7 @@ def cases_g8p():
             C("g8p-r-511x512x128-ldcN+8", "g8p_pers", 16, "real", 511, 512, 128, ldc=520, res=True, ldr=528, also="ldc+8"),
             C("g8p-x-511x512x128-ldcN+8", "g8p_pers", 16, "exact", 511, 512, 128, ldc=520, also="ldc+8"),
             C("g8p-r-589x512x128-ldw", "g8p_pers", 16, "real", 589, 512, 128, ldw=136, also="ldw"),
-            C("g8p-r-4096x256x128-h-stats", "g8p_pers", 16, "real", 4096, 256, 128, f16=True, res=True, also="stats"),
-            C("g8p-tile-x-256x8448x128", "g8p_tile", 16, "exact", 256, 8448, 128, also="tile"),
-            C("g8p-tile-r-256x8448x128", "g8p_tile", 16, "real", 256, 8448, 128, res=True, also="tile")]
+            C("g8p-r-4096x256x128-h-stats", "g8p_pers", 16, "real", 4096, 256, 128, f16=True, res=True, also="stats")]
     return out
 
 
@@ -362,8 +357,7 @@ def shrunk_cases():
             C("s-b256-r-3x300x260x64", "g256_batch", -1, "real", 300, 260, 64, api="batched", S=3, w_mod=3, bias=False),
             C("s-b256-x-3x300x260x64", "g256_batch", -1, "exact", 300, 260, 64, api="batched", S=3, w_mod=1, bias=False, out=32),
             C("s-g8p-x-300x256x448-twice", "g8p_pers", 16, "exact", 300, 256, 448, res=True), C("s-g8p-r-300x256x128-twice", "g8p_pers", 16, "real", 300, 256, 128, res=True),
-            C("s-g8p-r-300x256x128-gelu-h", "g8p_pers", 16, "real", 300, 256, 128, act=1, f16=True), C("s-g8p-r-300x256x128-qgelu32", "g8p_pers", 16, "real", 300, 256, 128, act=2, out=32, res=True),
-            C("s-g8p-tile-x-256x512x128", "g8p_tile", 16, "exact", 256, 512, 128), C("s-g8p-tile-r-256x512x128", "g8p_tile", 16, "real", 256, 512, 128, res=True)]
+            C("s-g8p-r-300x256x128-gelu-h", "g8p_pers", 16, "real", 300, 256, 128, act=1, f16=True), C("s-g8p-r-300x256x128-qgelu32", "g8p_pers", 16, "real", 300, 256, 128, act=2, out=32, res=True)]
 
 
 # ================================================================================================ layout and inputs

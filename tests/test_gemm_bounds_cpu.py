@@ -51,13 +51,13 @@ def test_every_case_lands_on_the_path_its_list_names():
             assert c.act == 0 and not (c.out == 16 and c.res and c.K < 128), c.id
     for name, f in G.CASE_LISTS.items():
         want = {"bf128x64": {"bf128x64"}, "bf128x128": {"bf128x128"}, "f16": {"h128x64", "h128x128"}, "g256": {"g256"}, "g256_batch": {"g256_batch"},
-                "batched128": {"bf128_batched"}, "g8p": {"g8p_pers", "g8p_tile"}}[name]
+                "batched128": {"bf128_batched"}, "g8p": {"g8p_pers"}}[name]
         assert {c.path for c in f()} == want, name
     # the refusals of sc_gemm8p_try and the thresholds of the dispatcher, on shapes next to the lists'
     base = G._c("t", "g8p_pers", 16, "real", 512, 512, 128)
     assert G.gemm8p_try(base, 16) == ("g8p_pers", "static", 0)
     for bad in (base._replace(N=520), base._replace(M=255), base._replace(K=64), base._replace(ldc=516), base._replace(res=True, ldr=516), base._replace(lda=132),
-                base._replace(ldw=132), base._replace(N=8448, M=257), base._replace(N=8448, out=32), base._replace(N=8448, f16=True)):
+                base._replace(ldw=132), base._replace(N=8448), base._replace(N=8448, M=257), base._replace(N=8448, out=32), base._replace(N=8448, f16=True)):
         assert G.gemm8p_try(bad, 16) is None, bad
     assert G.gemm8p_try(base._replace(ldc=516, out=32), 16) is not None                            # fp32 rows need 16 bytes = 4 elements only
     assert G.gemm8p_try(base._replace(K=384, M=2048), 16)[1] == "dyn" and G.gemm8p_try(base._replace(K=384, M=2048), 26)[1] == "static"
@@ -137,8 +137,10 @@ def test_case_lists_hold_the_required_shapes():
     assert any(c.mode == -1 and G.dispatch(c)["band"] == 4 and (c.M, c.N) == (2125, 4096) for c in p)
     assert any(c.lda < c.K for c in p) and any(c.lda > c.K for c in p) and any(c.ldc == c.N + 8 for c in p) and any(c.ldw > c.K for c in p)
     assert any(c.kind == "exact" and c.out == 16 and c.res and G.rounding_points(c) == "twice" for c in p)
-    t = [c for c in L["g8p"] if c.path == "g8p_tile"]
-    assert t and all((c.M, c.N, c.K, c.out) == (256, 8448, 128, 16) for c in t)
+    # N > 8192 under mode 16: sc_gemm8p_try declines and the 33 tiles run on gemm_bf16_kernel<128, 128>
+    t = [c for c in L["bf128x128"] if c.also == "declined8p"]
+    assert {c.kind for c in t} == {"exact", "real"} and len(t) == 2 and all((c.M, c.N, c.K) == (256, 8448, 128) and c.mode == 16 for c in t)
+    assert all(G.gemm8p_try(c, c.mode) is None and G.dispatch(c)["path"] == "bf128x128" and G.dispatch(c)["last_path"] == 0 for c in t)
     # every test stays short: no reference above the tile-switch shape's; and no case with more than 2e7 outputs, where the sign-weighted statistic's own
     # expectation under exact rounding (gemm_ref's docstring) would come close to 6 / sqrt(n)
     assert max(G.nprod(c) * c.M * c.N for c in G.all_cases()) <= 20_000_000

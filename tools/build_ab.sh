@@ -3,6 +3,8 @@
 # objects into tools/ab/lib<name>.so; run the two libraries in the same gpurun call with SPEECHCLIP_HIP_LIB=tools/ab/lib<name>.so.
 #   tools/build_ab.sh attention.hip "-DSC_ATTN_ABL=1" noexp        # working-tree source + flags
 #   tools/build_ab.sh gemm.hip "" old HEAD~3                       # the file as of a revision
+# (gemm.hip / gemm8p.hip of a revision that still defines glds16 itself need that revision's common.h and gemm8p.h beside them: compile the two by hand,
+#  as profiles/gemm8p_delab_timing.txt did, and link as below)
 set -e
 ROOT=$(cd "$(dirname "$0")/.." && pwd)
 SRC=$1; EXTRA=$2; NAME=${3:-B}; REV=$4

@@ -1,6 +1,8 @@
 #!/usr/bin/env python3
 """The GEMM kernels behind sc_gemm_bf16 side by side (sc_debug_set_gemm_mode): correctness against fp32 torch on a spread of shapes, then sustained-clock timing on the step's shapes.
-usage: duet_check.py [check] [time] [--sustain S] [--modes 0,4,8]"""
+usage: gemm_modes_check.py [check] [time] [trace8pp] [--sustain S] [--modes 0,16] [shape names]
+modes: 0 gemm256_kernel / gemm_bf16_kernel only, 16 gemm8p_pers_kernel wherever the shape allows, 26 the same with the static tile order, 99 the hipBLASLt
+comparator (time only; plain shapes), -1 the dispatcher's rule.  The library maps any other number to -1."""
 import sys, os, time, json
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
@@ -21,7 +23,7 @@ def ref(a, w, bias, act, res):
     return y
 
 
-CHECK_MODES = [0, 4, 8]
+CHECK_MODES = [0, 16]
 
 
 def check():
@@ -125,40 +127,6 @@ def timeit(sustain, modes, only):
     print(json.dumps(res))
 
 
-def trace8p(only):
-    """PROBES library: per-tile phases of gemm8p_kernel (mode 17): prologue / k-loop / epilogue cycles per wave, block lifetime and gaps."""
-    import ctypes
-    L = lib()
-    L.sc_debug_set_gemm_trace.argtypes = [ctypes.c_void_p]
-    for name, M, N, K, lda, act, use_res in SHAPES:
-        if only and name not in only:
-            continue
-        ld = lda or K
-        a = (torch.randn(M * ld + K + 64, device="cuda") * 0.5).to(torch.bfloat16)
-        w = (torch.randn(N, K, device="cuda") * K ** -0.5).to(torch.bfloat16)
-        bias = torch.randn(N, device="cuda")
-        resid = torch.randn(M, N, device="cuda").to(torch.bfloat16) if use_res else None
-        out = torch.empty(M, N, device="cuda", dtype=torch.bfloat16)
-        L.sc_debug_set_gemm_mode(17)
-        for _ in range(10):
-            ops.gemm(a, w, bias, act, resid, out=out, M=M, K=K, lda=ld)
-        tr = torch.zeros(4096 * 64, dtype=torch.int64, device="cuda")
-        L.sc_debug_set_gemm_trace(tr.data_ptr())
-        ops.gemm(a, w, bias, act, resid, out=out, M=M, K=K, lda=ld)
-        torch.cuda.synchronize()
-        L.sc_debug_set_gemm_trace(None)
-        ntiles = min(4096, (M // 256) * (N // 256))
-        t = tr.reshape(4096, 8, 8)[:ntiles].double()
-        nk = K // 64
-        pro, loop, epi = t[:, :, 0].mean(), t[:, :, 1].mean(), t[:, :, 2].mean()
-        life = (t[:, :, 4].max(dim=1).values - t[:, :, 3].min(dim=1).values).mean()
-        span = t[:, :, 4].max() - t[:, :, 3][t[:, :, 3] > 0].min()
-        print(f"{name}: per tile: prologue {pro:7.0f}  loop {loop:7.0f} ({loop/nk:6.0f} per k-step)  epilogue+drain {epi:7.0f}  block lifetime {life:7.0f}; "
-              f"{ntiles} traced tiles span {span:.0f} cycles = {span/ (ntiles/256):.0f} per round of 256", flush=True)
-        L.sc_debug_set_gemm_mode(-1)
-        del a, w, out, resid
-
-
 def trace8pp(only):
     """PROBES library: gemm8p_pers_kernel (mode 16): per tile, cycles in the first k-step (incl. waiting for the partner's epilogue), the others, the epilogue."""
     import ctypes
@@ -239,7 +207,7 @@ def trace(only, modes):
 if __name__ == "__main__":
     args = sys.argv[1:]
     sustain = 1.0
-    modes = [0, 4, 8]
+    modes = [0, 16]
     only = []
     global MODES
     i = 0
@@ -247,7 +215,7 @@ if __name__ == "__main__":
     while i < len(args):
         if args[i] == "--sustain": sustain = float(args[i + 1]); i += 2
         elif args[i] == "--modes": modes = [int(v) for v in args[i + 1].split(",")]; i += 2
-        elif args[i] in ("check", "time", "trace", "trace8p", "trace8pp"): todo.append(args[i]); i += 1
+        elif args[i] in ("check", "time", "trace", "trace8pp"): todo.append(args[i]); i += 1
         else: only.append(args[i]); i += 1
     if not todo: todo = ["check", "time"]
     MODES = modes
@@ -255,6 +223,5 @@ if __name__ == "__main__":
     if "check" in todo: ok = check()
     if "time" in todo: timeit(sustain, modes, only)
     if "trace" in todo: trace(only, modes)
-    if "trace8p" in todo: trace8p(only)
     if "trace8pp" in todo: trace8pp(only)
     sys.exit(0 if ok else 1)

@@ -10,7 +10,7 @@ usage: python tools/make_traffic_json.py <pmc_FETCH_SIZE dir> <pmc_WRITE_SIZE di
 import collections, csv, glob, json, os, sys
 
 
-GEMM_KERNELS = ("gemm256_kernel", "gemm_bf16_kernel", "gemm8p_pers_kernel", "gemm8p_kernel")      # every kernel behind sc_gemm_bf16 (round 5: + gemm8p)
+GEMM_KERNELS = ("gemm256_kernel", "gemm_bf16_kernel", "gemm8p_pers_kernel")      # every kernel behind sc_gemm_bf16 (round 5: + gemm8p)
 
 
 def act_of(k):
