@@ -767,6 +767,39 @@ int sc_search_items_bf16(const void* q, int64_t ld_q, const void* g, int64_t ld_
 int sc_topk_merge_items(const float* vals_in, const int64_t* idx_in, const int32_t* items_in, int Q, int L, int K, int distinct, float* vals, int64_t* idx,
                         int32_t* items, void* stream);
 
+/* ---- Gallery search by subset: sc_search_items / sc_search_items_bf16 inside a part of the gallery (csrc/search_select.hip) -- one split of an index that
+ * holds several, one language, or for every query the rows of its own class.  Two conjuncts join eligible(i, j), inside the fused kernel and BEFORE the
+ * top-K filter, and the scan skips the gallery tiles that nobody selected.  sc_search_select takes fp32 rows, sc_search_select_bf16 bf16 rows.  Everything
+ * not named here is sc_search_items / sc_search_items_bf16 of the same format: scores bit for bit, order, distinct, q_skip, the outputs and their missing
+ * slots (-inf / -1 / -1), strides, alignment, the rules for E, K, N and n_split, sc_search_splits, sc_search_items_workspace_bytes, the merge by
+ * sc_topk_merge_items, and every refusal.  SUBSET CONTRACT (restated on the host in tests/search_select_ref.py):
+ *   eligible   eligible(i, j) of sc_search_items, and allowed(j), and grouped(i, j).
+ *   row mask   allowed(j) means: g_allow == NULL, or bit (j & 31) of g_allow[j >> 5] is set.  j is the row number inside this call (0 .. N-1), not
+ *              idx_base + j.  Bits at j >= N are ignored, whatever they hold; ceil(N / 32) words are read and nothing beyond them.
+ *   group      grouped(i, j) means: q_group == NULL, or q_group[i] < 0, or g_group[j] == q_group[i].  g_group is int32 [N] with codes >= 0, q_group int32
+ *              [Q]; both are given or neither.
+ *   identity   with g_allow, g_group and q_group all NULL the result equals sc_search_items[_bf16] bit for bit.
+ *   few rows   a query with fewer than K eligible rows gets missing slots; that is not an error.
+ *   dead tiles a block's range is cut into tiles of 128 rows from the range's first row; a tile none of whose rows inside the range is allowed is DEAD: the
+ *              block issues no global loads of its g rows, no LDS stage and no MFMA for it, and prefetches the next LIVE tile's first chunk during the
+ *              current multiply.  Ranges are ceil(N / n_split) rows and in general neither word- nor tile-aligned: the first and last word of a tile are
+ *              masked to its rows.  Without g_allow every tile is live; groups skip nothing.  A block whose whole range is dead still writes its empty
+ *              K-list to the workspace.  The rows of dead tiles and the rows that are not eligible may hold anything (NaN, +-inf): the result does not change.
+ *   pure       as sc_search_items, with g_allow[0 .. ceil(N / 32)), g_group[:N] and q_group[i] added to what row i depends on.  No global atomics; the walk
+ *              over the live tiles is wave-uniform arithmetic on the mask words (a ballot over 64 tiles), the same in every wave of the block.
+ *   reads      what sc_search_items reads, except the g rows of dead tiles; g_allow[0 .. ceil(N / 32)), g_group[0 .. N) and q_group[0 .. Q) if given.
+ *   refused    (nonzero rc + sc_last_error naming the value, nothing launched) every refusal of sc_search_items[_bf16], and g_group without q_group or
+ *              q_group without g_group.  Q == 0 returns 0 and launches nothing.
+ * sc_pack_row_mask: mask uint8 [N] -> words uint32 [ceil(N / 32)]: words[j >> 5] bit (j & 31) = mask[j] != 0; the unused high bits of the last word are
+ *   written as 0; every word is written once.  N must be in [0, 2^31); N == 0 returns 0 and launches nothing; a null operand is refused. */
+int sc_search_select(const float* q, int64_t ld_q, const float* g, int64_t ld_g, int Q, int64_t N, int E, int K, int n_split, int64_t idx_base,
+                     const uint32_t* g_allow, const int32_t* g_group, const int32_t* q_group, const int32_t* g_item, const int32_t* q_skip, int distinct,
+                     float* vals, int64_t* idx, int32_t* items, void* workspace, void* stream);
+int sc_search_select_bf16(const void* q, int64_t ld_q, const void* g, int64_t ld_g, int Q, int64_t N, int E, int K, int n_split, int64_t idx_base,
+                          const uint32_t* g_allow, const int32_t* g_group, const int32_t* q_group, const int32_t* g_item, const int32_t* q_skip, int distinct,
+                          float* vals, int64_t* idx, int32_t* items, void* workspace, void* stream);
+int sc_pack_row_mask(const uint8_t* mask, int64_t N, uint32_t* words, void* stream);
+
 /* ---- Gallery search, fp32 re-score of a shortlist: the second stage of a two-stage search (csrc/search_rescore.hip).  A bf16 search (sc_search_topk_bf16 /
  * sc_search_items_bf16 on the rounded rows) shortlists R >= K rows per query; this entry scores those rows on the fp32 rows, returns the first K of them and
  * says per query whether an error bound given by the caller PROVES that the first K of the shortlist are the first K of the whole gallery.

@@ -189,6 +189,9 @@ def _declare(L):
         "sc_search_items": ([P, L64, P, L64, I, L64, I, I, I, L64, P, P, I, P, P, P, P, P], c_int),
         "sc_search_items_bf16": ([P, L64, P, L64, I, L64, I, I, I, L64, P, P, I, P, P, P, P, P], c_int),
         "sc_topk_merge_items": ([P, P, P, I, I, I, I, P, P, P, P], c_int),
+        "sc_search_select": ([P, L64, P, L64, I, L64, I, I, I, L64, P, P, P, P, P, I, P, P, P, P, P], c_int),
+        "sc_search_select_bf16": ([P, L64, P, L64, I, L64, I, I, I, L64, P, P, P, P, P, I, P, P, P, P, P], c_int),
+        "sc_pack_row_mask": ([P, L64, P, P], c_int),
         "sc_search_rescore": ([P, L64, P, L64, I, L64, I, P, P, I, P, I, L64, P, P, P, P], c_int),
         "sc_search_range_count": ([P, L64, P, L64, I, L64, I, P, I, P, P, P, L64, P], c_int),
         "sc_search_range_fill": ([P, L64, P, L64, I, L64, I, P, I, P, P, L64, P, L64, P, P, P], c_int),

@@ -16,6 +16,11 @@
 //                     fold and for the output, so both selections have the same four (WQ, list capacity) instantiations and LDS sizes (+ 4 bytes of skip
 //                     code per query row by item).
 // Everything by item stands under `if constexpr (ITEMS)`, its LDS array included: the plain instantiations hold none of it.
+// A third selection, BY SUBSET (SELECT, on top of ITEMS; search_select.hip, "Gallery search by subset"), adds two conjuncts to eligibility -- the row's bit in
+// a mask shared by all queries, and a group code the row must share with the query -- and walks only the LIVE tiles of the block's range, those with an
+// allowed row (next_live below): the mask words of a range are the same for every thread of the block, so every wave finds the same next tile by a ballot,
+// with no LDS list, no barrier and no atomics.  Everything by subset stands under `if constexpr (SELECT)`, its LDS array (a group code per query row) and
+// its loop control included: the other instantiations compile to what they compiled to without it.
 //
 // The operand format OP (search_rows.h) supplies what differs between fp32 and bf16 rows -- loading, staging and the product:
 //   elem                   storage type of a q / g element
@@ -44,11 +49,14 @@ static inline int query_rows_per_block(int Q, int K) { return K <= 64 && Q > 64 
 
 // WQ: 32-row query tiles per wave (block = 64 WQ query rows x 128 gallery rows, waves 2 x 2); KL: list capacity (K <= KL).
 // By item only (the plain kernels pass null / 0): g_item int32 [N], q_skip int32 [Q] or null, distinct, out_c.
-template <class OP, bool ITEMS, int WQ, int KL>
+// By subset only (SELECT, on top of ITEMS): g_allow uint32 [ceil(N / 32)] or null, g_group int32 [N] and q_group int32 [Q] or both null.
+template <class OP, bool ITEMS, int WQ, int KL, bool SELECT = false>
 __device__ __forceinline__ void search_block(const typename OP::elem* __restrict__ q, int64_t ld_q, const typename OP::elem* __restrict__ g, int64_t ld_g, int Q,
                                              int N, int E, int K, int per, int S, int64_t idx_base, const int32_t* __restrict__ g_item,
                                              const int32_t* __restrict__ q_skip, int distinct, float* __restrict__ out_v, int64_t* __restrict__ out_i,
-                                             int32_t* __restrict__ out_c) {
+                                             int32_t* __restrict__ out_c, const uint32_t* __restrict__ g_allow = nullptr,
+                                             const int32_t* __restrict__ g_group = nullptr, const int32_t* __restrict__ q_group = nullptr) {
+    static_assert(ITEMS || !SELECT, "the selection by subset extends the selection by item");
     using elem = typename OP::elem;
     constexpr int LDT = OP::LDT;
     constexpr int BQ = 64 * WQ;
@@ -66,17 +74,24 @@ __device__ __forceinline__ void search_block(const typename OP::elem* __restrict
         __shared__ int sk[BQ];         // (hipcc orders a kernel's LDS by the arrays' names: renaming one moves the others)
         skips = sk;
     }
+    int* groups = nullptr;             // by subset: the row's group code, -1: no restriction
+    if constexpr (SELECT) {
+        __shared__ int sg_q[BQ];
+        groups = sg_q;
+    }
 
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, r = lane & 31, h = lane >> 5;
     const int wq = wave >> 1, wg = wave & 1;
     const int q0 = blockIdx.x * BQ, s = blockIdx.y;
     const int jbeg = (int)min((int64_t)N, (int64_t)s * per), jend = (int)min((int64_t)N, (int64_t)jbeg + per);
     const bool has_skip = ITEMS && q_skip != nullptr;
+    const bool has_group = SELECT && q_group != nullptr;
 
     for (int x = tid; x < BQ * KL; x += 256) { lv[x] = -INFINITY; lj[x] = NO_J; }
     for (int x = tid; x < BQ; x += 256) {
         cnt[x] = 0;
         if constexpr (ITEMS) skips[x] = has_skip && q0 + x < Q ? q_skip[q0 + x] : -1;
+        if constexpr (SELECT) groups[x] = has_group && q0 + x < Q ? q_group[q0 + x] : -1;
     }
     // (the first __syncthreads of the tile loop, or the one before the output, orders these writes)
 
@@ -195,10 +210,39 @@ __device__ __forceinline__ void search_block(const typename OP::elem* __restrict
             OP::load(g + (int64_t)row * ld_g, row < jend, e, E, pg[u]);
         }
     };
-    if (total > 0) prefetch(0);
+    // by subset: the first LIVE tile at or after `from` -- a tile with an allowed row inside the block's range; ntiles if there is none.  Lane l of every
+    // wave tests tile from + l (the words that hold its rows, the first and the last masked to the rows), a ballot names the first: wave-uniform, the same
+    // in all four waves, no LDS and no atomics.  Only words [jbeg >> 5, (jend - 1) >> 5] are read.
+    auto next_live = [&](int from) {
+        if (g_allow == nullptr) return from;
+        for (int base = from; base < ntiles; base += 64) {
+            const int t = base + lane;
+            bool live = false;
+            if (t < ntiles) {
+                const int a = jbeg + t * BN, b = min(a + BN, jend) - 1;      // rows a .. b, a <= b < jend
+                for (int w = a >> 5; w <= b >> 5; ++w) {
+                    uint32_t bits = g_allow[w];
+                    if (w == a >> 5) bits &= ~0u << (a & 31);
+                    if (w == b >> 5) bits &= ~0u >> (31 - (b & 31));
+                    live |= bits != 0;
+                }
+            }
+            const uint64_t any = __ballot(live);
+            if (any) return base + (int)__builtin_ctzll(any);
+        }
+        return ntiles;
+    };
+    int first = 0, nxt = 0;                                  // by subset: the first live tile and the live tile after the current one
+    if constexpr (SELECT) {
+        first = next_live(0);
+        if (first < ntiles) prefetch(first * nchunk);
+    } else {
+        if (total > 0) prefetch(0);
+    }
 
     f32x16_t acc[WQ][2];
-    for (int tile = 0, it = 0; tile < ntiles; ++tile) {
+    for (int tile = first, it = first * nchunk; tile < ntiles; ++tile) {
+        if constexpr (SELECT) nxt = next_live(tile + 1);     // its first chunk is prefetched during this tile's last multiply
 #pragma unroll
         for (int a = 0; a < WQ; ++a)
 #pragma unroll
@@ -215,6 +259,18 @@ __device__ __forceinline__ void search_block(const typename OP::elem* __restrict
                 }
             }
         }
+        int jg[2] = {-1, -1};                                // by subset: group codes and allow bits of the same two rows
+        bool ja[2] = {true, true};
+        if constexpr (SELECT) {
+#pragma unroll
+            for (int b = 0; b < 2; ++b) {
+                const int j = jbeg + tile * BN + wg * 64 + b * 32 + r;
+                if (j < jend) {
+                    if (has_group) jg[b] = g_group[j];
+                    if (g_allow != nullptr) ja[b] = (g_allow[j >> 5] >> (j & 31)) & 1;
+                }
+            }
+        }
         for (int chunk = 0; chunk < nchunk; ++chunk, ++it) {
             __syncthreads();
 #pragma unroll
@@ -222,7 +278,12 @@ __device__ __forceinline__ void search_block(const typename OP::elem* __restrict
 #pragma unroll
             for (int u = 0; u < NGU; ++u) OP::store(sG + (urow + 32 * u) * LDT + uc8, pg[u]);
             __syncthreads();
-            if (it + 1 < total) prefetch(it + 1);            // the next stage's global loads are in flight during the multiply
+            if constexpr (SELECT) {                          // the next stage's global loads are in flight during the multiply
+                const int ahead = chunk + 1 == nchunk ? nxt * nchunk : it + 1;
+                if (ahead < total) prefetch(ahead);
+            } else {
+                if (it + 1 < total) prefetch(it + 1);        // the next stage's global loads are in flight during the multiply
+            }
             OP::template stage<WQ>(acc, sQ + (wq * 32 * WQ + r) * LDT, sG + (wg * 64 + r) * LDT, h, chunk * KC, E);
         }
         // ---- selection: accumulator (a, b, x) of this lane is query row i = wq*32*WQ + 32a + (x&3) + 8(x>>2) + 4h, gallery row j below
@@ -236,11 +297,14 @@ __device__ __forceinline__ void search_block(const typename OP::elem* __restrict
                 const int tj = lj[i * KL + K - 1];
                 int skip = -1;
                 if constexpr (ITEMS) skip = skips[i];
+                int group = -1;
+                if constexpr (SELECT) group = groups[i];
 #pragma unroll
                 for (int b = 0; b < 2; ++b) {
                     const int j = jbeg + tile * BN + wg * 64 + b * 32 + r;
                     bool eligible = true;                    // (a NaN score is before nothing)
                     if constexpr (ITEMS) eligible = skip < 0 || jc[b] != skip;
+                    if constexpr (SELECT) eligible = eligible && ja[b] && (group < 0 || jg[b] == group);
                     if (j < jend && q0 + i < Q && eligible && before(acc[a][b][x], j, tv, tj)) pend |= 1ull << ((a * 2 + b) * 16 + x);
                 }
             }
@@ -281,6 +345,7 @@ __device__ __forceinline__ void search_block(const typename OP::elem* __restrict
                         }
             }
         }
+        if constexpr (SELECT) { tile = nxt - 1; it = nxt * nchunk; }     // on to the next live tile (the loop adds the 1)
     }
     __syncthreads();
     compact(true);
@@ -301,11 +366,14 @@ __device__ __forceinline__ void search_block(const typename OP::elem* __restrict
 //   e_mul / ld_mul   what E and the row strides must be multiples of in this operand format (fp32 rows: 4 / 4, bf16 rows: 16 / 8)
 //   kern             the entry's score kernel at (WQ, KL) = (2, 16) (2, 64) (1, 16) (1, 128): the wide tile where query_rows_per_block says so, the short
 //                    list for K <= 16
-// The plain entries (ITEMS == false) pass null g_item / q_skip / items and distinct = 0; nothing reads them.
-template <class OP, bool ITEMS, class KERN>
+// The plain entries (ITEMS == false) pass null g_item / q_skip / items and distinct = 0; nothing reads them.  The entries by subset (SELECT, search_select.hip)
+// add g_allow / g_group / q_group, each of which may be null; the groups are given together or not at all.
+template <class OP, bool ITEMS, bool SELECT = false, class KERN>
 int search_host(const char* name, int e_mul, int ld_mul, KERN* const (&kern)[4], const typename OP::elem* q, int64_t ld_q, const typename OP::elem* g,
                 int64_t ld_g, int Q, int64_t N, int E, int K, int n_split, int64_t idx_base, const int32_t* g_item, const int32_t* q_skip, int distinct, float* vals,
-                int64_t* idx, int32_t* items, void* workspace, void* stream) {
+                int64_t* idx, int32_t* items, void* workspace, void* stream, const uint32_t* g_allow = nullptr, const int32_t* g_group = nullptr,
+                const int32_t* q_group = nullptr) {
+    static_assert(ITEMS || !SELECT, "the selection by subset extends the selection by item");
     SC_CHECK_ARG(E >= e_mul && E <= 1024 && E % e_mul == 0, "%s: E=%d must be a multiple of %d in [%d, 1024]", name, E, e_mul, e_mul);
     SC_CHECK_ARG(ld_q >= E && ld_g >= E && ld_q % ld_mul == 0 && ld_g % ld_mul == 0, "%s: ld_q=%lld / ld_g=%lld must be multiples of %d and >= E=%d", name,
                  (long long)ld_q, (long long)ld_g, ld_mul, E);
@@ -321,6 +389,9 @@ int search_host(const char* name, int e_mul, int ld_mul, KERN* const (&kern)[4],
         SC_CHECK_ARG(g_item, "%s: null g_item (an int32 item code per gallery row is required)", name);
         SC_CHECK_ARG(items, "%s: null items", name);
     }
+    if constexpr (SELECT)
+        SC_CHECK_ARG((g_group == nullptr) == (q_group == nullptr), "%s: g_group and q_group are given together or not at all (%s is null)", name,
+                     g_group ? "q_group" : "g_group");
     const int S = n_split ? n_split : sc_search_splits(Q, N, K);
     SC_CHECK_ARG(S == 1 || workspace, "%s: %d splits need a workspace (%s)", name, S, ITEMS ? "sc_search_items_workspace_bytes" : "sc_search_workspace_bytes");
     const int per = (int)((N + S - 1) / S);
@@ -332,7 +403,10 @@ int search_host(const char* name, int e_mul, int ld_mul, KERN* const (&kern)[4],
     const int bq = query_rows_per_block(Q, K);
     const dim3 grid((unsigned)((Q + bq - 1) / bq), (unsigned)S);
     KERN* const k = kern[(bq == 128 ? 0 : 2) + (K <= 16 ? 0 : 1)];
-    if constexpr (ITEMS)
+    if constexpr (SELECT)
+        hipLaunchKernelGGL(k, grid, dim3(256), 0, (hipStream_t)stream, q, ld_q, g, ld_g, Q, (int)N, E, K, per, S, idx_base, g_item, q_skip, distinct, ov, oi,
+                           S == 1 ? items : wc, g_allow, g_group, q_group);
+    else if constexpr (ITEMS)
         hipLaunchKernelGGL(k, grid, dim3(256), 0, (hipStream_t)stream, q, ld_q, g, ld_g, Q, (int)N, E, K, per, S, idx_base, g_item, q_skip, distinct, ov, oi,
                            S == 1 ? items : wc);
     else

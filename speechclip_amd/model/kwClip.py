@@ -144,11 +144,15 @@ class KWClipBase(BaseLightningModel):
             raise ValueError("give exactly one of images, sents, wav, with at least one item")
         return index
 
-    def search(self, index: EmbeddingIndex, k: int, images=None, sents=None, wav=None, distinct: bool = False, exclude=None, rerank=None):
+    def search(self, index: EmbeddingIndex, k: int, images=None, sents=None, wav=None, distinct: bool = False, exclude=None, rerank=None,
+               allow=None, allow_ids=None, within=None, row_groups=None, query_groups=None):
         """The k nearest items of `index` for every query of one modality -> (scores f32 [Q, k], positions i64 [Q, k], ids): EmbeddingIndex.search.
         distinct=True: the k nearest different ids (an index of several captions per image answers with images); exclude: one id per query to leave out
-        (hard negatives: the nearest items that are not the query's own); rerank=R: the same result by the two-stage search of an index with a shadow."""
-        return index.search(self._embed(images=images, sents=sents, wav=wav), k, distinct=distinct, exclude=exclude, rerank=rerank)
+        (hard negatives: the nearest items that are not the query's own); rerank=R: the same result by the two-stage search of an index with a shadow.
+        allow / allow_ids / within / row_groups + query_groups: search a subset of the gallery only (within: one id per query, only the rows carrying it --
+        a query's own positives), as EmbeddingIndex.search takes them."""
+        return index.search(self._embed(images=images, sents=sents, wav=wav), k, distinct=distinct, exclude=exclude, rerank=rerank, allow=allow,
+                            allow_ids=allow_ids, within=within, row_groups=row_groups, query_groups=query_groups)
 
     def search_range(self, index: EmbeddingIndex, min_score, images=None, sents=None, wav=None, exclude=None, max_results=None):
         """Every item of `index` that scores at least min_score (one number, or one per query) for every query of one modality -> (lims i64 [Q + 1],

@@ -52,6 +52,14 @@ def rerank_kappa(E: int) -> float:
     return (2.0 ** -7 + 2.0 ** -16) + 2.0 * E * u / (1.0 - 2.0 * E * u) * (1.0 + 2.0 ** -8) ** 2 + E * u / (1.0 - E * u)
 
 
+class RowSelector:
+    """A row subset of one EmbeddingIndex, prepared once (EmbeddingIndex.selector) and passed to search(allow=...): `words` holds, per segment, the packed
+    mask (uint32 [ceil(rows / 32)], bit j & 31 of word j >> 5 = row j of THAT segment is allowed); `rows` is what the index held when it was made."""
+
+    def __init__(self, index: "EmbeddingIndex", words: List[torch.Tensor], rows: int):
+        self.index, self.words, self.rows = index, words, rows
+
+
 class EmbeddingIndex:
     """A gallery of embeddings on the device and the answer to "which k stored items are nearest to this query?" (sc_search_topk: fused fp32
     similarity + top-k, no [Q, N] score image).  Rows are kept as fp32 SEGMENTS, one per `add`; adding never reallocates earlier segments.  A search runs
@@ -85,6 +93,7 @@ class EmbeddingIndex:
         self.ids: Optional[list] = None            # None: the ids are the running positions
         self._n = 0
         self._codes = None                         # item codes of the rows (search with distinct / exclude), derived from ids
+        self._code_table = None                    # their host half: (codes per row or None, {id: code} or None, number of codes)
 
     def __len__(self) -> int:
         return self._n
@@ -125,7 +134,7 @@ class EmbeddingIndex:
             self._n += n
             if self.shadow:
                 self._add_shadow(rows)
-        self._codes = None
+        self._codes = self._code_table = None
         return self
 
     def _add_shadow(self, rows: torch.Tensor) -> None:
@@ -147,8 +156,8 @@ class EmbeddingIndex:
         """-> (one int32 device tensor of item codes per segment, {id: code} or None, number of codes).  Equal ids share a code, assigned in first-seen
         order; without ids the code is the position.  Derived from `ids`, built on first use and dropped by `add`; never stored."""
         if self._codes is None:
-            table = None if self.ids is None else {}
-            codes = list(range(self._n)) if table is None else [table.setdefault(x, len(table)) for x in self.ids]
+            codes, table, _ = self._item_codes_host()
+            codes = list(range(self._n)) if codes is None else codes
             segs, at = [], 0
             for seg in self.segments:
                 segs.append(torch.tensor(codes[at:at + seg.shape[0]], dtype=torch.int32, device=seg.device))
@@ -156,8 +165,95 @@ class EmbeddingIndex:
             self._codes = (segs, table, self._n if table is None else len(table))
         return self._codes
 
+    def selector(self, allow=None, allow_ids=None) -> "RowSelector":
+        """A reusable row subset for search(allow=...): the packed mask words of every segment, on the device.  allow: bool [len(index)] by position;
+        allow_ids: a collection of ids, selecting the rows that carry one of them (ids the index does not hold select nothing) -- the lookup over the
+        stored ids is paid here, once, not per search.  The selector speaks about the rows the index holds NOW: it refuses to be used after a later add."""
+        if (allow is None) == (allow_ids is None):
+            raise ValueError("a selector takes allow (a bool per row) or allow_ids (a collection of ids), one of the two")
+        mask = self._allow_mask(allow, allow_ids)
+        return self._pack_selector(mask)
+
+    def _allow_mask(self, allow, allow_ids) -> torch.Tensor:
+        """Host rules of allow / allow_ids -> a bool tensor [len(index)] (wherever the caller's lives; from ids: on the host)."""
+        if allow_ids is not None:
+            wanted = set(allow_ids.detach().cpu().tolist() if torch.is_tensor(allow_ids) else allow_ids)
+            ids = range(self._n) if self.ids is None else self.ids
+            return torch.tensor([x in wanted for x in ids], dtype=torch.bool)
+        mask = torch.as_tensor(allow)
+        if mask.dtype != torch.bool or mask.shape != (self._n,):
+            raise ValueError(f"allow must be a bool per stored row [{self._n}], got {tuple(mask.shape)} {mask.dtype}")
+        return mask
+
+    def _pack_selector(self, mask: torch.Tensor) -> "RowSelector":
+        from .. import ops
+        mask = mask.to(self._device())
+        words, at = [], 0
+        for seg in self.segments:                  # every segment's slice is packed from ITS row 0: a segment is one call of the entry
+            words.append(ops.pack_row_mask(mask[at:at + seg.shape[0]].contiguous()))
+            at += seg.shape[0]
+        return RowSelector(self, words, self._n)
+
+    def _select_arguments(self, queries, allow, allow_ids, within, row_groups, query_groups, rerank):
+        """The host rules of the subset arguments of `search`, checked before anything touches the device -> None without any of them, else
+        (selector or bool mask or None, row groups (host or device int tensor) or None, the queries' group codes as a host list or None, within?)."""
+        if all(x is None for x in (allow, allow_ids, within, row_groups, query_groups)):
+            return None
+        if rerank is not None:
+            raise ValueError("rerank with allow / allow_ids / within / row_groups is not supported: the certificate speaks about the whole gallery, "
+                             "not about a subset of it")
+        if allow is not None and allow_ids is not None:
+            raise ValueError("allow and allow_ids exclude each other: give the subset by position or by id")
+        if (row_groups is None) != (query_groups is None):
+            raise ValueError("row_groups and query_groups are given together or not at all")
+        if within is not None and row_groups is not None:
+            raise ValueError("within cannot be combined with row_groups: within IS row_groups = the item codes and query_groups = the id's code")
+        Q = len(queries)
+        q_codes = None
+        if within is not None:
+            within = within.detach().cpu().tolist() if torch.is_tensor(within) else list(within)
+            if len(within) != Q:
+                raise ValueError(f"{len(within)} within ids for {Q} queries")
+            _, table, n_ids = self._item_codes_host()
+            # an id the index does not hold, or None, matches nothing: the code n_ids, which no row carries (a negative code would lift the restriction)
+            if table is None:
+                q_codes = [x if isinstance(x, int) and not isinstance(x, bool) and 0 <= x < self._n else n_ids for x in within]
+            else:
+                q_codes = [n_ids if x is None else table.get(x, n_ids) for x in within]
+        if row_groups is not None:
+            row_groups = torch.as_tensor(row_groups)
+            if row_groups.is_floating_point() or row_groups.dtype == torch.bool or row_groups.shape != (self._n,):
+                raise ValueError(f"row_groups must be an int per stored row [{self._n}], got {tuple(row_groups.shape)} {row_groups.dtype}")
+            # (the same rule wherever the tensor lives: of a device tensor this reads two numbers back, before any search is launched)
+            if row_groups.numel() and not 0 <= int(row_groups.min()) <= int(row_groups.max()) < 2 ** 31:
+                raise ValueError("row_groups must hold values in [0, 2^31)")
+            q_codes = query_groups.detach().cpu().tolist() if torch.is_tensor(query_groups) else list(query_groups)
+            if len(q_codes) != Q:
+                raise ValueError(f"{len(q_codes)} query_groups for {Q} queries")
+            if any(isinstance(x, bool) or not isinstance(x, int) or not -2 ** 31 <= x < 2 ** 31 for x in q_codes):
+                raise ValueError("query_groups must hold one int per query (negative: no restriction)")
+        subset = None
+        if isinstance(allow, RowSelector):
+            if allow.index is not self:
+                raise ValueError("this selector was made by another index")
+            if allow.rows != self._n:
+                raise ValueError(f"this selector was made when the index held {allow.rows} rows; it holds {self._n} now: make a new one after add")
+            subset = allow
+        elif allow is not None or allow_ids is not None:
+            subset = self._allow_mask(allow, allow_ids)
+        return subset, row_groups, q_codes, within is not None
+
+    def _item_codes_host(self):
+        """The host half of _item_codes -> (the code of every row as a list, or None without ids; {id: code} or None; number of codes): the argument rules
+        run before the device is touched.  The one pass over the ids, built on first use, kept until `add`, and what _item_codes puts on the device."""
+        if self._code_table is None:
+            table = None if self.ids is None else {}
+            codes = None if table is None else [table.setdefault(x, len(table)) for x in self.ids]
+            self._code_table = (codes, table, self._n if table is None else len(table))
+        return self._code_table
+
     def search(self, queries: torch.Tensor, k: int, distinct: bool = False, exclude: Optional[Sequence[Hashable]] = None, rerank: Optional[int] = None,
-               return_certified: bool = False):
+               return_certified: bool = False, allow=None, allow_ids=None, within=None, row_groups=None, query_groups=None):
         """-> (scores f32 [Q, k] descending, positions i64 [Q, k], ids): ids[i][r] is the stored id of positions[i, r] (the position itself without ids).
         distinct=True: the k nearest DIFFERENT ids, each by its best row (rows that share an id are one item; k <= the number of different ids).
         exclude: one id per query (a sequence of len(queries)); rows carrying it are left out of that query's result -- None, or an id the index does not
@@ -165,10 +261,18 @@ class EmbeddingIndex:
         rerank=R (an index with a shadow, k <= R <= 128, distinct=False): the SAME result, bit for bit, by two stages -- a bf16 search of the shadow rows
         shortlists R rows per query and segment, sc_search_rescore scores them on the fp32 rows and certifies the queries whose shortlist provably holds
         the first k (rerank_kappa), and only the other queries go through the fp32 search.  return_certified=True (with rerank) appends a bool [Q] host
-        tensor: which queries the certificate covered."""
+        tensor: which queries the certificate covered.
+        A SUBSET of the gallery (sc_search_select: the predicate acts before the top-k filter, and gallery tiles nobody selected are not scanned):
+        allow = a bool per stored row, by position, or a prepared index.selector(...); allow_ids = a collection of ids, selecting the rows that carry one
+        of them (ids the index does not hold select nothing; allow and allow_ids exclude each other); row_groups (an int >= 0 per stored row) with
+        query_groups (an int per query, negative: no restriction): query i sees only the rows of its group; within = one id per query: only the rows
+        carrying that id take part -- the converse of exclude, shorthand for row_groups = the item codes (an id the index does not hold, or None, matches
+        nothing; not with row_groups).  A query with fewer than k rows left gets -inf / -1 / None in the last slots.  Nothing of this combines with
+        rerank.  With none of these arguments exactly the entries above run."""
         from .. import ops
         k = int(k)
-        if rerank is not None:                     # the rules of the two-stage search are host rules: checked before anything touches the device
+        select = self._select_arguments(queries, allow, allow_ids, within, row_groups, query_groups, rerank)
+        if rerank is not None:                    # the rules of the two-stage search are host rules: checked before anything touches the device
             if not self.shadow:
                 raise ValueError("rerank needs an index with shadow rows: EmbeddingIndex(..., shadow=True) or index.with_shadow()")
             if distinct:
@@ -182,24 +286,52 @@ class EmbeddingIndex:
             raise ValueError(f"k={k} must be in [1, min(128, {self._n} stored rows)]")
         if rerank is not None:
             return self._search_rerank(queries, k, int(rerank), bool(distinct), exclude, bool(return_certified))
-        distinct, by_item = bool(distinct), bool(distinct) or exclude is not None
+        distinct, by_item = bool(distinct), bool(distinct) or exclude is not None or select is not None
         codes, skip = self._item_arguments(queries, k, distinct, exclude) if by_item else ([None] * len(self.segments), None)
         q = self._rows(queries)
         if skip is not None:
             skip = torch.tensor(skip, dtype=torch.int32, device=dev)
-        scores, pos = self._search_prepared(q, k, distinct, by_item, codes, skip)
+        if select is not None:
+            select = self._select_on_device(select, codes, dev)
+        scores, pos = self._search_prepared(q, k, distinct, by_item, codes, skip, select)
         return scores, pos, self._ids_of(pos)
 
-    def _search_prepared(self, q: torch.Tensor, k: int, distinct: bool, by_item: bool, codes, skip):
-        """The one-stage search of prepared query rows (already normalised and in the storage type) -> (scores, positions)."""
+    def _select_on_device(self, select, codes, dev):
+        """What _select_arguments returned -> (mask words per segment, group codes per segment, the queries' group codes), each a device tensor or None."""
+        subset, row_groups, q_codes, by_within = select
+        none = [None] * len(self.segments)
+        words = none if subset is None else (subset if isinstance(subset, RowSelector) else self._pack_selector(subset)).words
+        groups, q_group = none, None
+        if q_codes is not None:
+            q_group = torch.tensor(q_codes, dtype=torch.int32, device=dev)
+            if by_within:
+                groups = codes                     # within: the rows' groups are their item codes
+            else:
+                row_groups = row_groups.to(dev, torch.int32)
+                groups, at = [], 0
+                for seg in self.segments:          # every segment gets its own slice, as it gets its own slice of the mask
+                    groups.append(row_groups[at:at + seg.shape[0]].contiguous())
+                    at += seg.shape[0]
+        return words, groups, q_group
+
+    def _search_prepared(self, q: torch.Tensor, k: int, distinct: bool, by_item: bool, codes, skip, select=None):
+        """The one-stage search of prepared query rows (already normalised and in the storage type) -> (scores, positions).  select: the subset arguments
+        on the device (_select_on_device) or None; with it every segment goes through sc_search_select[_bf16], else through exactly the entries of before."""
         from .. import ops
         dev = q.device
         bf16 = self.storage == "bf16"
         search_topk, search_items = (ops.search_topk_bf16, ops.search_items_bf16) if bf16 else (ops.search_topk, ops.search_items)
+        search_select = ops.search_select_bf16 if bf16 else ops.search_select
+        none = [None] * len(self.segments)
+        words, groups, q_group = select if select is not None else (none, none, None)
         parts, base = [], 0
-        for seg, code in zip(self.segments, codes):
+        for seg, code, word, group in zip(self.segments, codes, words, groups):
             kk = min(k, seg.shape[0])
-            part = search_items(q, seg, kk, code, q_skip=skip, distinct=distinct, idx_base=base) if by_item else search_topk(q, seg, kk, idx_base=base)
+            if select is not None:
+                part = search_select(q, seg, kk, code, allow=word, g_group=group if q_group is not None else None, q_group=q_group, q_skip=skip,
+                                     distinct=distinct, idx_base=base)
+            else:
+                part = search_items(q, seg, kk, code, q_skip=skip, distinct=distinct, idx_base=base) if by_item else search_topk(q, seg, kk, idx_base=base)
             if kk < k:                             # a segment shorter than k: its list is padded with entries that take no part in the merge
                 part = [torch.cat([t, torch.full((q.shape[0], k - kk), fill, device=dev, dtype=t.dtype)], 1) for t, fill in zip(part, (float("-inf"), -1, -1))]
             parts.append(part)

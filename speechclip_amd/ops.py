@@ -1071,9 +1071,10 @@ def retrieval_ranks(score, own_ids, cand_ids):
 
 
 # ---- gallery search (search.hip, search_bf16.hip, search_items.hip) ----
-def _search(entry, dtype, q, g, k, n_split, idx_base, workspace, by_item=None):
-    """The four entries of the fused search: the same shapes, split rule and (vals, idx) outputs; `entry` and the rows' dtype differ.  by_item = (g_item,
-    q_skip, distinct) selects by item (sc_search_items*): the item codes of the gallery rows, the queries' skip codes or None, and a third output."""
+def _search(entry, dtype, q, g, k, n_split, idx_base, workspace, by_item=None, select=None):
+    """The entries of the fused search: the same shapes, split rule and (vals, idx) outputs; `entry` and the rows' dtype differ.  by_item = (g_item,
+    q_skip, distinct) selects by item (sc_search_items*): the item codes of the gallery rows, the queries' skip codes or None, and a third output.
+    select = (allow, g_group, q_group), with by_item, selects inside a subset (sc_search_select*): each of the three may be None."""
     _need_cuda(q, g)
     assert q.dtype == dtype and g.dtype == dtype and q.dim() == 2 and g.dim() == 2 and q.stride(1) == 1 and g.stride(1) == 1
     assert q.shape[1] == g.shape[1], (q.shape, g.shape)
@@ -1090,6 +1091,18 @@ def _search(entry, dtype, q, g, k, n_split, idx_base, workspace, by_item=None):
             assert q_skip.dtype == torch.int32 and q_skip.shape == (Q,) and q_skip.is_contiguous(), (q_skip.dtype, q_skip.shape)
         out.append(torch.empty(Q, k, device=q.device, dtype=torch.int32))
         extra, workspace_bytes = (ptr(g_item), ptr(q_skip), int(bool(distinct))), lib().sc_search_items_workspace_bytes
+    if select is not None:
+        allow, g_group, q_group = select
+        if allow is not None:
+            _need_cuda(allow)
+            assert allow.dtype == torch.uint32 and allow.shape == ((N + 31) // 32,) and allow.is_contiguous(), (allow.dtype, allow.shape)
+        if g_group is not None:
+            _need_cuda(g_group)
+            assert g_group.dtype == torch.int32 and g_group.shape == (N,) and g_group.is_contiguous(), (g_group.dtype, g_group.shape)
+        if q_group is not None:
+            _need_cuda(q_group)
+            assert q_group.dtype == torch.int32 and q_group.shape == (Q,) and q_group.is_contiguous(), (q_group.dtype, q_group.shape)
+        extra = (ptr(allow), ptr(g_group), ptr(q_group)) + extra
     nbytes = workspace_bytes(Q, N, k, int(n_split))
     if workspace is None and nbytes > 0:
         workspace = torch.empty(nbytes, device=q.device, dtype=torch.uint8)
@@ -1136,6 +1149,31 @@ def search_items(q, g, k, g_item, q_skip=None, distinct=False, n_split=0, idx_ba
 def search_items_bf16(q, g, k, g_item, q_skip=None, distinct=False, n_split=0, idx_base=0, workspace=None):
     """search_items on bf16 rows: search_topk_bf16's scores under the same selection (sc_search_items_bf16)."""
     return _search("sc_search_items_bf16", bf16, q, g, k, n_split, idx_base, workspace, (g_item, q_skip, distinct))
+
+
+def search_select(q, g, k, g_item, allow=None, g_group=None, q_group=None, q_skip=None, distinct=False, n_split=0, idx_base=0, workspace=None):
+    """search_items inside a subset of the gallery (sc_search_select): allow uint32 [ceil(N / 32)] (pack_row_mask) holds one bit per gallery row, shared by
+    all queries; g_group i32 [N] (codes >= 0) and q_group i32 [Q] restrict query i to the rows with g_group[j] == q_group[i] (q_group[i] < 0: no restriction;
+    both or neither).  A row takes part iff search_items lets it and its bit is set and its group matches.  Gallery tiles of 128 rows without an allowed row
+    are not loaded.  With all three None this is search_items bit for bit; a query with fewer than k eligible rows gets missing slots (-inf / -1 / -1)."""
+    return _search("sc_search_select", torch.float32, q, g, k, n_split, idx_base, workspace, (g_item, q_skip, distinct), (allow, g_group, q_group))
+
+
+def search_select_bf16(q, g, k, g_item, allow=None, g_group=None, q_group=None, q_skip=None, distinct=False, n_split=0, idx_base=0, workspace=None):
+    """search_select on bf16 rows: search_items_bf16's scores under the same selection (sc_search_select_bf16)."""
+    return _search("sc_search_select_bf16", bf16, q, g, k, n_split, idx_base, workspace, (g_item, q_skip, distinct), (allow, g_group, q_group))
+
+
+def pack_row_mask(mask):
+    """mask bool or uint8 [N] (device) -> uint32 [ceil(N / 32)]: bit (j & 31) of word j >> 5 says whether mask[j] != 0; the unused high bits of the last word
+    are 0 (sc_pack_row_mask).  What search_select takes as `allow`."""
+    _need_cuda(mask)
+    assert mask.dtype in (torch.bool, torch.uint8) and mask.dim() == 1, (mask.dtype, mask.shape)
+    mask = mask.contiguous().view(torch.uint8)
+    N = mask.shape[0]
+    words = torch.empty((N + 31) // 32, device=mask.device, dtype=torch.uint32)
+    check(lib().sc_pack_row_mask(ptr(mask), N, ptr(words), stream()), "sc_pack_row_mask")
+    return words
 
 
 def topk_merge_items(vals, idx, items, k, distinct):
