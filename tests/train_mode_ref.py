@@ -1,5 +1,6 @@
 """Plain fp64 restatements of the TRAIN-MODE paths (dropout sites of the frozen encoder, of the fine-tuning nodes and of the pooling head) for
-tests/test_train_mode_parity_gpu.py and tools/train_mode_bounds.py.  A helper module, not a test; no kernel runs here.
+tests/test_train_mode_parity_gpu.py and tools/train_mode_bounds.py.  A helper module, not a test; no kernel runs here.  tests/train_nodes_ref.py builds on it
+(the pre-LN body, the layer mix, the branch stack and the image tower, for tests/test_train_nodes_parity_gpu.py).
 
 Every function is torch autograd in fp64 on the CPU, one utterance at a time (it never sees a neighbour).  Masks come in as TENSORS that already hold
 keep / (1 - p), so a mutant is just another mask (or one of the few `wiring` switches).  The keep bits themselves are the restatements of
@@ -184,10 +185,10 @@ def layer_masks(seeds4, layout, b, n, d, ffn, H, rates, **attn_kw):
 
 
 # ================================================================================================ the fairseq post-LN layer
-def post_ln_layer(x, params, lens, masks=None, model=False, eps=1e-5, bwd_masks=None, wiring=(), fused_ln=False):
+def post_ln_layer(x, params, lens, masks=None, model=False, eps=1e-5, bwd_masks=None, wiring=(), fused_ln=False, heads=None):
     """x fp64 [B, T, d]; params: the 16 tensors of train_hubert.layer_params (fp64); lens: valid keys per utterance (keys >= lens[b] are masked, every query
     row is computed); masks: dict(attn [B, H, T, T], d1 [B, T, d], d2 [B, T, ffn], d3 [B, T, d]) of keep / (1 - p), None = no dropout at that site.
-    x = LN(x + dropout1(attn(x)));  x = LN(x + dropout3(fc2(dropout2(gelu(fc1 x)))))    (head_dim 64).  Stack it by feeding the output back in.
+    x = LN(x + dropout1(attn(x)));  x = LN(x + dropout3(fc2(dropout2(gelu(fc1 x)))))    (heads: None = head_dim 64).  Stack it by feeding the output back in.
     bwd_masks: MUTANT -- masks the backward applies instead.  wiring: MUTANTS -- "residual_masked" (the mask also on the residual path).
     fused_ln: the frozen encoder at d = 768 (sc_dropout_add_layernorm_bf16): residual + dropout(x) is not stored before the LayerNorm."""
     R = Rounder(model)
@@ -195,7 +196,8 @@ def post_ln_layer(x, params, lens, masks=None, model=False, eps=1e-5, bwd_masks=
     bm = bwd_masks or {}
     qw, qb, kw, kb, vw, vb, ow, ob, g1, b1n, w1, b1, w2, b2, g2, b2n = params
     B, T, d = x.shape
-    H, hd = d // 64, 64
+    H = heads or d // 64
+    hd = d // H
     wqkv = torch.cat([R.w16(qw), R.w16(kw), R.w16(vw)], 0)
     qkv = R.rs(x @ wqkv.t() + torch.cat([qb, kb, vb]))                                 # qkv (forward) / dqkv (backward)
     q, k, v = [t.view(B, T, H, hd).transpose(1, 2) for t in qkv.split(d, dim=-1)]
@@ -228,11 +230,16 @@ def post_ln_layer(x, params, lens, masks=None, model=False, eps=1e-5, bwd_masks=
     return R.rs(F.layer_norm(y2, (d,), g2, b2n, eps))                                   # the layer's output / the gradient it receives
 
 
-def layer_node(xs, layers, lens, masks, dhidden, train, model=False, bwd_masks=None, wiring=()):
-    """train_hubert.HubertLayersTrainFn over a list of utterances: xs[b] fp64 [T_b, d]; layers[li]: 16 fp64 tensors; lens[b] valid keys; masks[li][b] (layer_masks);
-    dhidden[li][b] fp64 [T_b, d]: the gradient of hidden state li.  -> dict(hidden[li][b], dh_in[b], grads[li] = 16 tensors or None where train[li] is False)."""
+def layer_node(xs, layers, lens, masks, dhidden, train, model=False, bwd_masks=None, wiring=(), pre_ln=False, act="gelu"):
+    """train_hubert.HubertLayersTrainFn over a list of utterances: xs[b] fp64 [T_b, d]; layers[li]: 16 fp64 tensors; lens[b] valid keys; masks[li][b] (layer_masks,
+    or None: no dropout); dhidden[li][b] fp64 [T_b, d]: the gradient of hidden state li.  Any number of layers, any `train` tuple (a frozen layer still passes the
+    gradient down).  pre_ln: the pre-LN body on an fp32 stream (train_nodes_ref.pre_ln_layer, activation `act`); there the sum of the stream gradient and the direct
+    gradient of a hidden state is stored in bf16 once more (sc_axpy_bf16).  wiring: the bodies' MUTANTS plus "no_direct" (the direct gradient of hidden[li - 1]
+    not added).  -> dict(hidden[li][b], dh_in[b], grads[li] = 16 tensors or None where train[li] is False)."""
     R = Rounder(model)
     n = len(layers)
+    if pre_ln:
+        from train_nodes_ref import pre_ln_layer
     P = [[p.detach().clone().requires_grad_(True) for p in lp] for lp in layers]
     leaves = [x.detach().clone().requires_grad_(True) for x in xs]
     hidden = [[None] * len(xs) for _ in range(n)]
@@ -240,9 +247,13 @@ def layer_node(xs, layers, lens, masks, dhidden, train, model=False, bwd_masks=N
     for b, x in enumerate(leaves):
         h = R.rb(x)[None]                                                               # dh_in: bf16
         for li in range(n):
-            out = post_ln_layer(h, P[li], [lens[b]], masks[li][b], model, bwd_masks=None if bwd_masks is None else bwd_masks[li][b], wiring=wiring)
+            if pre_ln:
+                out = R.rb(pre_ln_layer(h, P[li], [lens[b]], masks[li][b], model, act, wiring=wiring))      # the join with the direct gradient, stored in bf16
+            else:
+                out = post_ln_layer(h, P[li], [lens[b]], masks[li][b], model, bwd_masks=None if bwd_masks is None else bwd_masks[li][b], wiring=wiring)
             hidden[li][b] = out[0]
-            loss = loss + (out[0] * dhidden[li][b]).sum()
+            if li == n - 1 or "no_direct" not in wiring:
+                loss = loss + (out[0] * dhidden[li][b]).sum()
             h = R.rb(out)                                                               # dh of the layer above, stored before the direct gradient is added
     flat = [p for li in range(n) if train[li] for p in P[li]]
     got = torch.autograd.grad(loss, leaves + flat, allow_unused=True)
