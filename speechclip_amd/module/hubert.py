@@ -39,7 +39,8 @@ _CONV0_LN_FUSED = os.environ.get("SC_CONV0_LN_FUSED", "1") != "0"
 # outputs and the layer weights carry 11 significand bits instead of bf16's 8; the residual stream is fp32 either way.  This is the precision the reference runs
 # these models at on a GPU (fp16 autocast: config/speechCLIP/model_large/coco/spchclp_p.yaml:122); 24 layers of bf16 operand rounding were what held the
 # P-large parity floor at 0.985.  SC_PRELN_F16=0 (A/B): bf16 operands, rounds 1-5.  Post-LN models (HuBERT-base) keep bf16: their residual
-# stream itself is 16-bit, and bf16's range is what that needs.
+# stream itself is 16-bit, and bf16's range is what that needs.  The conversion to half is unsaturated (a value above 65504 becomes inf); the half-range case of
+# tests/test_infer_nodes_parity_gpu.py pins the in-range behaviour (a stored GELU output of 2^15 .. 6e4 keeps the ordinary bound).
 _PRELN_F16 = os.environ.get("SC_PRELN_F16", "1") != "0"
 
 

@@ -189,7 +189,8 @@ def post_ln_layer(x, params, lens, masks=None, model=False, eps=1e-5, bwd_masks=
     """x fp64 [B, T, d]; params: the 16 tensors of train_hubert.layer_params (fp64); lens: valid keys per utterance (keys >= lens[b] are masked, every query
     row is computed); masks: dict(attn [B, H, T, T], d1 [B, T, d], d2 [B, T, ffn], d3 [B, T, d]) of keep / (1 - p), None = no dropout at that site.
     x = LN(x + dropout1(attn(x)));  x = LN(x + dropout3(fc2(dropout2(gelu(fc1 x)))))    (heads: None = head_dim 64).  Stack it by feeding the output back in.
-    bwd_masks: MUTANT -- masks the backward applies instead.  wiring: MUTANTS -- "residual_masked" (the mask also on the residual path).
+    bwd_masks: MUTANT -- masks the backward applies instead.  wiring: MUTANTS -- "residual_masked" (the mask also on the residual path), "res2_from_h" (the second
+    residual taken from the layer's input instead of LayerNorm 1's output: tests/infer_nodes_ref.py).
     fused_ln: the frozen encoder at d = 768 (sc_dropout_add_layernorm_bf16): residual + dropout(x) is not stored before the LayerNorm."""
     R = Rounder(model)
     masks = masks or {}
@@ -221,7 +222,7 @@ def post_ln_layer(x, params, lens, masks=None, model=False, eps=1e-5, bwd_masks=
         hm = R.rs(mask(hm, masks["d2"], bm.get("d2")))                                  # hm after dropout2 (in place) / dhm
     f = hm @ R.w16(w2).t() + b2
     if masks.get("d3") is None:
-        y2 = f + x1
+        y2 = f + (x if "res2_from_h" in wiring else x1)
     else:
         f = R.rs(f)                                                                     # fc2's bf16 output / dy2 (the masked gradient)
         y2 = mask(f + x1, masks["d3"], bm.get("d3")) if sub else mask(f, masks["d3"], bm.get("d3")) + x1
@@ -354,26 +355,37 @@ def pool_keep(seed, B, R, n_keys, stride, p, lens=None, NQ=0, share_rows=False):
 
 
 # ================================================================================================ the frozen encoder in train mode
-def conv_stack(enc, wav_b, length, model=False):
+def conv_stack(enc, wav_b, length, model=False, conv0_fused=True, wave_len=None, gn_frames=None):
     """The conv feature extractor of module.hubert.HubertModel `enc` on ONE utterance's own zero-padded wave [lmax] -> fp64 [T, C] (GroupNorm statistics over
-    the padded length, as the engine computes them).  model=True: bf16 conv 1-6 weights and a bf16 store of every layer's output."""
+    the padded length, as the engine computes them).  model=True: bf16 conv 1-6 weights and a bf16 store of every layer's output; a "layer_norm" extractor also
+    stores the conv output in bf16 in front of its LayerNorm (layer 0 only when conv0_fused is False: the fused kernel keeps it in registers).
+    MUTANTS: wave_len -- the wave LayerNorm (cfg.normalize) over this many samples instead of the utterance's own `length`; gn_frames -- the GroupNorm statistics
+    over the first gn_frames frames (the utterance's own) instead of all frames of the padded length."""
     cfg = enc.cfg
     st = r16 if model else (lambda t: t)
     w16 = (lambda t: r16(t.detach())) if model else (lambda t: t.detach().double())
     d64 = lambda t: None if t is None else t.detach().double()      # noqa: E731
     x = wav_b.double().clone()
     if cfg.normalize:
-        x[:length] = F.layer_norm(x[:length], (length,))
+        n = length if wave_len is None else wave_len
+        x[:n] = F.layer_norm(x[:n], (n,))
+        x[length:] = 0                                          # the padding stays zero (sc_wave_layernorm writes zeros there)
     y = None
     for i, blk in enumerate(enc.feature_extractor.conv_layers):
         c = getattr(blk, "0")
         y = F.conv1d(x[None, None] if i == 0 else y, d64(c.weight) if i == 0 else w16(c.weight), d64(getattr(c, "bias", None)), stride=cfg.conv_layers[i][2])
         if cfg.extractor_mode == "layer_norm":
             ln = getattr(getattr(blk, "2"), "1")
+            if i > 0 or not conv0_fused:
+                y = st(y)
             y = F.layer_norm(y.transpose(1, 2), (y.shape[1],), d64(ln.weight), d64(ln.bias), 1e-5).transpose(1, 2)
         elif i == 0:
             gn = getattr(blk, "2")
-            y = F.group_norm(y, y.shape[1], d64(gn.weight), d64(gn.bias), 1e-5)
+            if gn_frames is None:
+                y = F.group_norm(y, y.shape[1], d64(gn.weight), d64(gn.bias), 1e-5)
+            else:
+                own = y[..., :gn_frames]
+                y = (y - own.mean(-1, keepdim=True)) / (own.var(-1, unbiased=False, keepdim=True) + 1e-5).sqrt() * d64(gn.weight)[None, :, None] + d64(gn.bias)[None, :, None]
         y = st(F.gelu(y))
     return y[0].t().contiguous()
 

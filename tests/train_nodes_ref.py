@@ -88,52 +88,57 @@ class _AttnStored(torch.autograd.Function):
         return p * ((dpd if ctx.m is None else dpd * ctx.m) - delta), pd.transpose(-1, -2) @ g, None, None, None
 
 
-def _attention(R, qkv, B, T, H, lens, m_attn, delta_stored=True):
-    """q | k | v [B, T, 3d] -> att [B, T, d]: keys >= lens[b] masked, every query computed; the rounding points of train_mode_ref.post_ln_layer."""
+def _attention(R, qkv, B, T, H, lens, m_attn, delta_stored=True, causal=False):
+    """q | k | v [B, T, 3d] -> att [B, T, d]: keys >= lens[b] masked, every query computed; the rounding points of train_mode_ref.post_ln_layer.
+    causal: query i also masks the keys > i (the text tower).  The 16-bit stores take the Rounder's format (bf16, or IEEE half for the frozen pre-LN encoder)."""
     d = qkv.shape[-1] // 3
     hd = d // H
     q, k, v = [t.view(B, T, H, hd).transpose(1, 2) for t in qkv.split(d, dim=-1)]
     s = R.rb((q @ k.transpose(-1, -2)) * hd ** -0.5)                                    # dS: the bf16 score gradient of the attention backward
-    dead = torch.arange(T)[None, :] >= torch.as_tensor(lens).view(B, 1)
-    o = _AttnStored.apply(s.masked_fill(dead[:, None, None, :], float("-inf")), v, m_attn, r16 if R.model else None, delta_stored)      # P, att / datt
+    dead = (torch.arange(T)[None, :] >= torch.as_tensor(lens).view(B, 1))[:, None, None, :]
+    if causal:
+        dead = dead | (torch.arange(T)[None, :] > torch.arange(T)[:, None] + (int(causal) - 1))          # causal = 2: MUTANT, key i + 1 admitted
+    o = _AttnStored.apply(s.masked_fill(dead, float("-inf")), v, m_attn, R.fmt if R.model else None, delta_stored)      # P, att / datt
     return o.transpose(1, 2).reshape(B, T, d)
 
 
 # ================================================================================================ the pre-LN layer body
-def pre_ln_layer(x, params, lens, masks=None, model=False, act="gelu", eps=1e-5, wiring=(), heads=None):
+def pre_ln_layer(x, params, lens, masks=None, model=False, act="gelu", eps=1e-5, wiring=(), heads=None, causal=False, fmt=r16):
     """train_hubert._layer_fwd_pre_ln / _layer_bwd_pre_ln.  x fp64 [B, T, d]: the fp32 residual stream; params: the 16 tensors of train_hubert.layer_params;
     lens: valid keys per utterance; masks: dict(attn, d1, d2, d3) of keep / (1 - p) or None (train_mode_ref.layer_masks); heads: None = d / 64.
         x += dropout1(out_proj(attn(LN1 x)));  x += dropout3(fc2(dropout2(act(fc1(LN2 x)))))
     The stream is stored in fp32; t1, q | k | v, the probabilities, att, t2, hm and the recomputed u in bf16.  Both LayerNorm backwards read the bf16 copy of the
     stream (h16, xmid16) and store a bf16 gradient; each residual join (sc_axpy_bf16) stores the sum in bf16 again.
     wiring (MUTANTS): "no_join_mid" / "no_join_h" (a residual join dropped: dxm without g / dh without dxm), "ln_from_out" (the LayerNorm backward fed t1 / t2),
-    "act_bwd_swapped" (the other activation's derivative)."""
-    R = Rounder(model)
+    "act_bwd_swapped" (the other activation's derivative), "res_after_ln" (both residuals taken behind the LayerNorm: t1 / t2 instead of the stream).
+    causal: the text tower's mask (query i sees keys <= i below lens[b]).  fmt: the format of every 16-bit store and weight operand -- r16, or the IEEE-half store of
+    the frozen pre-LN encoder layers (tests/infer_nodes_ref.py); forward-only wirings of the inference references are documented there."""
+    R = Rounder(model, fmt)
     masks = masks or {}
     qw, qb, kw, kb, vw, vb, ow, ob, g1, b1n, w1, b1, w2, b2, g2, b2n = params
     B, T, d = x.shape
     H = heads or d // 64
-    rnd = r16 if model else None
+    rnd = getattr(fmt, "plain", fmt) if model else None          # what only a backward reads (saved copies) goes past a probing format
     ln = lambda t, w, b: _LNStored.apply(R.rb(t), w, b, eps, rnd, "ln_from_out" in wiring)      # noqa: E731   R.rb: the bf16 dx the LayerNorm backward stores
     other = "quickgelu" if act == "gelu" else "gelu"
     h = R.rb(R.rf(x, r32))                                                              # the stream (fp32) / dh after the join, bf16
     t1 = R.rs(ln(h, g1, b1n))                                                           # t1 / dt1
-    wqkv = torch.cat([R.w16(qw), R.w16(kw), R.w16(vw)], 0)
+    wqkv = torch.cat([R.rf(qw), R.rf(kw), R.rf(vw)], 0)
     qkv = R.rs(t1 @ wqkv.t() + torch.cat([qb, kb, vb]))                                 # qkv / dqkv
     # the head_dim 64 backwards of train_hubert.py always take delta from the stored output, the head-dim kernel (heads given) whenever it does not drop
-    att = _attention(R, qkv, B, T, H, lens, masks.get("attn"), heads is None or masks.get("attn") is None)
-    o = att @ R.w16(ow).t() + ob
+    att = _attention(R, qkv, B, T, H, lens, masks.get("attn"), heads is None or masks.get("attn") is None, causal)
+    o = att @ R.rf(ow).t() + ob
     if masks.get("d1") is not None:
         o = R.rs(mask(R.rs(o), masks["d1"]))                                            # out_proj's bf16 output, dropped in place / dy1 = the masked dxm
-    xmid = R.rb(R.rf((_cut(h) if "no_join_h" in wiring else h) + o, r32))               # xmid (fp32) / dxm after the join, bf16
+    xmid = R.rb(R.rf((_cut(h) if "no_join_h" in wiring else t1 if "res_after_ln" in wiring else h) + o, r32))      # xmid (fp32) / dxm after the join, bf16
     t2 = R.rs(ln(xmid, g2, b2n))                                                        # t2 / dt2
-    hm = R.rs(_ActStored.apply(t2 @ R.w16(w1).t() + b1, rnd, act, other if "act_bwd_swapped" in wiring else act))      # hm / dhm; u recomputed and stored
+    hm = R.rs(_ActStored.apply(t2 @ R.rf(w1).t() + b1, rnd, act, other if "act_bwd_swapped" in wiring else act))      # hm / dhm; u recomputed and stored
     if masks.get("d2") is not None:
         hm = R.rs(mask(hm, masks["d2"]))
-    f = hm @ R.w16(w2).t() + b2
+    f = hm @ R.rf(w2).t() + b2
     if masks.get("d3") is not None:
         f = R.rs(mask(R.rs(f), masks["d3"]))                                            # fc2's bf16 output, dropped in place / dy2 = the masked g
-    return R.rf((_cut(xmid) if "no_join_mid" in wiring else xmid) + f, r32)             # the layer's output (fp32); its gradient arrives in bf16
+    return R.rf((_cut(xmid) if "no_join_mid" in wiring else t2 if "res_after_ln" in wiring else xmid) + f, r32)      # the layer's output (fp32); its gradient arrives in bf16
 
 
 # ================================================================================================ the layer mix
@@ -278,7 +283,8 @@ def image_tower_node(image, params, cfg, w, model=False, wiring=()):
     Stem: the patch GEMM on the bf16 patch columns and the bf16 kernel, output stored in bf16 (patch / dpatch); LN_pre([cls | patch] + pos) in fp32, recomputed in
     fp32 by the backward.  Blocks: pre_ln_layer with QuickGELU, no key mask.  Head: ln_post of the fp32 class rows stored in bf16, proj as a 16-bit operand with an
     fp32 output; its backward in fp32 from the fp32 master of proj; the class-row gradient enters a zero bf16 stream gradient.
-    wiring (MUTANTS): "seed_row1" (that gradient seeded on row 1), "dcls_cut" (class_embedding's gradient without the class row's share), plus pre_ln_layer's.
+    wiring (MUTANTS): "seed_row1" (that gradient seeded on row 1), "dcls_cut" (class_embedding's gradient without the class row's share), plus pre_ln_layer's;
+    of the forward (tests/infer_nodes_ref.py): "post_row1" (ln_post on row 1 instead of the class row), "no_ln_pre" (ln_pre left out).
     -> dict(feat [B, E], grads: name -> tensor)"""
     R = Rounder(model)
     P = {k: v.detach().clone().requires_grad_(True) for k, v in params.items()}
@@ -289,7 +295,7 @@ def image_tower_node(image, params, cfg, w, model=False, wiring=()):
     patch = R.rs(patch.reshape(B, W, -1).permute(0, 2, 1))                              # patch / dpatch, bf16
     ce = P["class_embedding"]
     v = torch.cat([(_cut(ce) if "dcls_cut" in wiring else ce).expand(B, 1, W), patch], 1) + P["positional_embedding"]
-    x = R.rf(F.layer_norm(v, (W,), P["ln_pre.weight"], P["ln_pre.bias"], eps), r32)
+    x = R.rf(v if "no_ln_pre" in wiring else F.layer_norm(v, (W,), P["ln_pre.weight"], P["ln_pre.bias"], eps), r32)
     for li in range(cfg["layers"]):
         pre = f"transformer.resblocks.{li}."
         iw, ib = P[pre + "attn.in_proj_weight"], P[pre + "attn.in_proj_bias"]
@@ -301,6 +307,8 @@ def image_tower_node(image, params, cfg, w, model=False, wiring=()):
     rows = x[:, 0]
     if "seed_row1" in wiring:
         rows = rows.detach() + (x[:, 1] - x[:, 1].detach())
+    if "post_row1" in wiring:
+        rows = x[:, 1]
     ncls = R.rf(F.layer_norm(rows, (W,), P["ln_post.weight"], P["ln_post.bias"], eps))  # ln_post's output, bf16
     feat = R.rf(_MatmulStored16.apply(ncls, P["proj"], model), r32)
     names = list(P)
